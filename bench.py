@@ -21,6 +21,12 @@ child process, before anything touches a GPU); the driver's own
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` is
 accepted too.  A WORLD_SIZE that disagrees with --gpus is an error (exit 2).
 
+A plain run sets up, warms up, times the --steps steps, checks the open statuses and prints the
+line.  `--full` adds every other leg after the timed steps (per-kernel seal / open timing and the
+rooflines, the cold-cache pass, forged-tag opens, the HBM copy ceiling, the strict byte check, the
+CPU baselines, `--e2e`, and with N > 1 the 1-GPU base, single-process and e2e_multi legs).
+`--dump-outputs DIR` writes what the last timed step left as DIR/<name>.npy (dump_outputs()).
+
 `--workload cfg1` times BASELINE config 1 instead: one 1500-B packet sealed and
 opened on one CPU thread (ns/packet), plus the per-message GPU drop-in.
 """
@@ -100,6 +106,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: per-kernel timing and rooflines, the "
+                         "cold-cache pass, forged-tag opens, the HBM copy ceiling, the strict byte check, the CPU "
+                         "baselines, --e2e, and with N > 1 the 1-GPU base, single-process and e2e_multi legs "
+                         "(off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left (sampled frames, statuses, block sums "
+                         "of the whole buffer) as DIR/<name>.npy")
     ap.add_argument("--workload", default=None, choices=["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"],
                     help="BASELINE config (default: cfg2 on one GPU, the cfg5 split on several)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per packet (0 = auto)")
@@ -115,23 +129,28 @@ def parse():
                     help="sub-batches per step: seal of part k+1 overlaps open of part k on a second stream")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured HIP graph")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="CPU baseline budget: port and OpenSSL, 1 thread and all cores, 5 runs each (0 = skip)")
+                    help="with --full: CPU baseline budget: port and OpenSSL, 1 thread and all cores, 5 runs each (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="all-core thread count (0 = this host's share)")
     ap.add_argument("--cpu-study", action="store_true",
                     help="only the CPU baselines' scaling study (free / pinned / pinned + private slices), no GPU")
-    ap.add_argument("--e2e", action="store_true", help="also time the pinned host->GPU->host path")
+    ap.add_argument("--e2e", action="store_true", help="with --full: also time the pinned host->GPU->host path")
     ap.add_argument("--single-process", action="store_true",
                     help="one process and one thread drive all --gpus N GPUs (rg_group: config 5's split, "
                          "rg_{seal,open}_batch_dev_multi) instead of one rank per GPU")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch/validate the ranks, print each rank's plan as JSON and exit before any GPU work")
     ap.add_argument("--forged", default="0.01,0.1",
-                    help="also time the open with these fractions of forged tags, comma-separated (0 = skip)")
+                    help="with --full: also time the open with these fractions of forged tags, comma-separated (0 = skip)")
     ap.add_argument("--no-cold", dest="cold", action="store_false",
-                    help="skip the cold-cache pass (profiling runs: keeps per-kernel averages to the step's regime)")
+                    help="with --full: skip the cold-cache pass (profiling runs: keeps per-kernel averages to the step's regime)")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
                     help="skip the status check after the timed region (on by default, outside the timing)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.e2e and not args.full:
+        ap.error("--e2e is one of the --full legs: add --full")
+    if args.dump_outputs and (args.single_process or args.cpu_study or args.workload == "cfg1"):
+        ap.error("--dump-outputs writes the timed step's buffers: not with --single-process, --cpu-study or cfg1")
+    return args
 
 
 def kernel_label(args, eng, w) -> str:
@@ -800,21 +819,22 @@ def bench_single_process(args):
                                   + f" (strong split over {args.gpus} GPU(s), one process, one thread)",
                       "parallelism": f"group{args.gpus} (one rg_ctx per GPU, no collective)"},
            "mpkt_s": sp["mpkt_s"], "single_process": sp}
-    try:
-        out["e2e_multi"] = e2e_multi_run(devices, verify=args.verify)
-    except Exception as e:  # the device-resident line stands without it
-        out["e2e_multi"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+    if args.full:
+        try:
+            out["e2e_multi"] = e2e_multi_run(devices, verify=args.verify)
+        except Exception as e:  # the device-resident line stands without it
+            out["e2e_multi"] = {"error": f"{type(e).__name__}: {e}"[:300]}
     if share:
         out["rehearsal"] = f"RG_BENCH_SHARE_GPU=1: {args.gpus} contexts on one GPU -- not a scaling measurement"
     print(json.dumps(out), flush=True)
 
 
 def run_legs(rank: int, world: int, workload: str, args) -> list:
-    """What a rank runs after the timed steps.  With N > 1 rank 0 also makes the line self-contained:
-    the same workload's whole batch on its one GPU (the strong-scaling base, `base_1gpu`) and the CPU
-    baselines; the other ranks wait at the final barrier."""
+    """What a rank runs: the timed steps, and with --full the legs after them.  With N > 1 rank 0 then also
+    makes the line self-contained: the same workload's whole batch on its one GPU (the strong-scaling
+    base, `base_1gpu`) and the CPU baselines; the other ranks wait at the final barrier."""
     legs = ["timed"]
-    if rank == 0:
+    if rank == 0 and args.full:
         if world > 1 and workload == "cfg5":
             legs.append("base_1gpu")
             legs.append("single_process")
@@ -980,6 +1000,45 @@ def e2e_multi_run(devices, reps: int = 3, verify: bool = True):
     return out
 
 
+DUMP_PACKETS = 4096        # sampled frames: at most 4096 x ~1.5 KB as float32 = 25 MB
+DUMP_STATUS_MAX = 1 << 20  # statuses: all of them up to 1 Mi packets (4 MB), else the sampled packets'
+DUMP_BLOCKS_MAX = 1 << 20  # block sums of the whole buffer: at most 1 Mi float64 (8 MB)
+
+
+def dump_outputs(dirname: str, w, b, rank: int, world: int):
+    """--dump-outputs: what the last timed step left in the buffers a caller handed in, as
+    DIR/<name>.npy (with N > 1 ranks DIR/<name>_rank<r>.npy), under 64 MB in all:
+      packets  float64  indices of the sampled packets: the first, the last and a fixed seeded draw
+      frames   float32  the sampled packets' whole frames after seal then open, one value per byte,
+                        concatenated in `packets` order: header, restored payload, and the tag the seal wrote
+      status   float32  the open's per-packet status (every packet, or the sampled ones beyond 1 Mi packets)
+      blocksum float64  byte sums of the whole frame buffer in equal blocks (the last one may be short)
+    The workload is generated from fixed seeds, so two runs with the same arguments write the same files."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(20240229)
+    pick = np.unique(np.concatenate([[0, w.n - 1], rng.choice(w.n, min(w.n, DUMP_PACKETS - 2), replace=False)]))
+    off = w.desc["offset"][pick].astype(np.int64)
+    ln = w.desc["len"][pick].astype(np.int64) + 32
+    idx = np.concatenate([np.arange(o, o + n_, dtype=np.int64) for o, n_ in zip(off, ln)])
+    frames = b.buf[torch.from_numpy(idx).to(b.buf.device)].cpu().numpy().astype(np.float32)
+    if w.n <= DUMP_STATUS_MAX:
+        status = b.status[: w.n].cpu().numpy().astype(np.float32)
+    else:
+        status = b.status[torch.from_numpy(pick.astype(np.int64)).to(b.status.device)].cpu().numpy().astype(np.float32)
+    total = int(b.buf.numel())
+    block = max(4096, -(-total // DUMP_BLOCKS_MAX))
+    whole = total // block
+    sums = b.buf[: whole * block].view(whole, block).sum(dim=1, dtype=torch.int64)
+    if whole * block < total:
+        sums = torch.cat([sums, b.buf[whole * block:].sum(dtype=torch.int64).reshape(1)])
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in (("packets", pick.astype(np.float64)), ("frames", frames), ("status", status),
+                      ("blocksum", sums.cpu().numpy().astype(np.float64))):
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), arr)
+
+
 def load_traffic(workload: str):
     p = os.path.join(REPO, "profiles", f"pmc_{workload}.json")
     if os.path.exists(p):
@@ -1015,7 +1074,9 @@ def main():
                 "local_rank": int(os.environ.get("LOCAL_RANK", "0")), "workload": workload}
         if world > 1:
             plan["legs"] = run_legs(plan["rank"], world, workload, args)
-        plan["forged"] = forged_fracs(args.forged)  # forged-open legs after the timed region
+        # forged-open legs after the timed region (--full)
+        fracs = forged_fracs(args.forged)
+        plan["forged"] = fracs if args.full else []
         line = json.dumps(plan) + "\n"
         os.write(1, line.encode())  # one write: ranks sharing the pipe never interleave a line
         return
@@ -1147,34 +1208,39 @@ def main():
     if args.verify:
         assert (b.status[: w.n] == 0).all().item(), "open failed after timed steps"
 
-    # per-kernel timing for the roofline: seal -> open pairs on the step's batch
-    # (the same work and cache state as a step), one HIP event pair around each
-    # launch on the launch stream, averaged over the pairs.  The stream is first held
-    # by a spin kernel while every pair is enqueued, so that the GPU runs them back to
-    # back: an event then brackets the kernel, not the host's time to submit it.
-    reps = max(args.steps, 10)
-    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(reps)]
-    with torch.cuda.stream(stream):
-        torch.cuda._sleep(int(2e7))  # ~10 ms of GPU clock cycles: longer than enqueueing the pairs
-    for e in evs:
-        e[0].record(stream)
-        b.seal(stream=stream)
-        e[1].record(stream)
-        e[2].record(stream)
-        b.open(stream=stream, counters_out=False)
-        e[3].record(stream)
-    torch.cuda.synchronize()
-    seal_each = sorted(e[0].elapsed_time(e[1]) for e in evs)
-    open_each = sorted(e[2].elapsed_time(e[3]) for e in evs)
-    seal_ms = sum(seal_each) / reps
-    open_ms = sum(open_each) / reps
-    if args.verify:
-        assert (b.status[: w.n] == 0).all().item(), "open failed in the kernel-timing pass"
-    cold = cold_cache_timing(eng, w, b, stream, args.verify) if args.cold and w.buf_bytes < MALL_BYTES else None
-    forged = [forged_open_timing(w, b, stream, f, args.verify) for f in forged_fracs(args.forged)] or None
-    copy_ceiling = hbm_copy_rate(stream) if rank == 0 else None
-    if args.verify:
-        strict_check(w, b, stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, b, rank, world)
+
+    seal_ms = open_ms = cold = forged = copy_ceiling = None
+    if args.full:
+        # per-kernel timing for the roofline: seal -> open pairs on the step's batch
+        # (the same work and cache state as a step), one HIP event pair around each
+        # launch on the launch stream, averaged over the pairs.  The stream is first held
+        # by a spin kernel while every pair is enqueued, so that the GPU runs them back to
+        # back: an event then brackets the kernel, not the host's time to submit it.
+        reps = max(args.steps, 10)
+        evs = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(reps)]
+        with torch.cuda.stream(stream):
+            torch.cuda._sleep(int(2e7))  # ~10 ms of GPU clock cycles: longer than enqueueing the pairs
+        for e in evs:
+            e[0].record(stream)
+            b.seal(stream=stream)
+            e[1].record(stream)
+            e[2].record(stream)
+            b.open(stream=stream, counters_out=False)
+            e[3].record(stream)
+        torch.cuda.synchronize()
+        seal_each = sorted(e[0].elapsed_time(e[1]) for e in evs)
+        open_each = sorted(e[2].elapsed_time(e[3]) for e in evs)
+        seal_ms = sum(seal_each) / reps
+        open_ms = sum(open_each) / reps
+        if args.verify:
+            assert (b.status[: w.n] == 0).all().item(), "open failed in the kernel-timing pass"
+        cold = cold_cache_timing(eng, w, b, stream, args.verify) if args.cold and w.buf_bytes < MALL_BYTES else None
+        forged = [forged_open_timing(w, b, stream, f, args.verify) for f in forged_fracs(args.forged)] or None
+        copy_ceiling = hbm_copy_rate(stream) if rank == 0 else None
+        if args.verify:
+            strict_check(w, b, stream)
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
     if dist is not None:
@@ -1185,22 +1251,6 @@ def main():
     total_payload = 2 * payload * args.steps * world  # seal + open
     total_pkts = 2 * w.n * args.steps * world
     value = total_payload / tmax / 2**30
-    seal_alg = 2 * payload + 32 * w.n        # read P, write P + header + tag
-    open_alg = 2 * payload + 33 * w.n        # read P + header + tag, write P + status
-    dominant = "seal" if seal_ms >= open_ms else "open"
-    dom_ms, dom_alg = (seal_ms, seal_alg) if dominant == "seal" else (open_ms, open_alg)
-    achieved = dom_alg / (dom_ms / 1e3) / 1e9
-    pmc = load_traffic(workload)
-    traffic = None
-    # only counters of the kernel family this run used (a kernel change makes them stale)
-    if pmc and pmc.get(dominant) and pmc[dominant].get("family") == eng.last_kernel():
-        traffic = pmc[dominant].get("hbm_bytes_per_launch")
-        n_pmc = pmc[dominant].get("packets_per_launch")
-        if traffic and n_pmc and n_pmc != w.n:
-            # counters taken on another shard size of the same geometry (config 5 on one GPU vs a rank's
-            # shard): HBM bytes per packet carried over
-            traffic = int(round(traffic * w.n / n_pmc))
-
     out = {
         "metric": METRIC,
         "value": round(value, 3),
@@ -1211,6 +1261,7 @@ def main():
         "ms_per_step": round(tmax / args.steps * 1e3, 4),
         "gpu_ms_per_step": round(step_ms, 5),
         "graph": graph is not None,
+        "full": args.full,
         "higher_is_better": True,
         "scaling": "strong" if workload == "cfg5" else "weak",
         "vs_baseline": None,
@@ -1226,34 +1277,54 @@ def main():
                    "kernel": kernel_label(args, eng, w), "split": args.split,
                    "wg_per_cu": args.wg_per_cu or "auto"},
         "mpkt_s": round(total_pkts / tmax / 1e6, 3),
-        "seal_ms": round(seal_ms, 5),
-        "open_ms": round(open_ms, 5),
-        "seal_ms_median": round(seal_each[reps // 2], 5),  # the median beside the mean
-        "open_ms_median": round(open_each[reps // 2], 5),
-        "seal_gib_s": round(payload / (seal_ms / 1e3) / 2**30 * world, 3),
-        "open_gib_s": round(payload / (open_ms / 1e3) / 2**30 * world, 3),
-        "seal_mpkt_s": round(w.n / (seal_ms / 1e3) / 1e6 * world, 3),
         # the same rate counted in wire bytes W = P + 32 per packet (header + tag), SURVEY §8(d)
         "wire_gib_s": round(2 * w.wire_bytes * args.steps * world / tmax / 2**30, 3),
     }
-    ceil_gbs = valu_ceiling_gbs(w.desc["len"], False)
-    out["roofline"], out["valu_roofline"] = rooflines(dominant, achieved, dom_alg, traffic, payload / (seal_ms / 1e3) / 1e9,
-                                                      ceil_gbs, KERNEL_CLOCK_GHZ.get(workload))
-    if pmc:
-        out["roofline"]["pmc_source"] = pmc.get("source")
-    if copy_ceiling:
-        # the spec peak stays the denominator; the copy rate is what a plain streaming kernel reaches here
-        out["roofline"]["copy_achievable"] = copy_ceiling
-        out["roofline"]["frac_of_copy"] = round(achieved / copy_ceiling["gb_s"], 4)
-    if cold:
-        # the cold-cache leg's own HBM roofline fraction (the step above runs on a cache-resident batch)
-        cold_dom_ms = cold["seal_ms"] if dominant == "seal" else cold["open_ms"]
-        cold["roofline"] = {"kernel": dominant, "achieved": round(dom_alg / (cold_dom_ms / 1e3) / 1e9, 2),
-                            "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": round(dom_alg / (cold_dom_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
-        cold["vs_warm"] = {"seal": round(cold["seal_ms"] / seal_ms, 3), "open": round(cold["open_ms"] / open_ms, 3),
-                           "gib_s": round(cold["gib_s"] / (2 * payload / ((seal_ms + open_ms) / 1e3) / 2**30), 3)}
-        out["cold_cache"] = cold
+    if args.full:
+        seal_alg = 2 * payload + 32 * w.n        # read P, write P + header + tag
+        open_alg = 2 * payload + 33 * w.n        # read P + header + tag, write P + status
+        dominant = "seal" if seal_ms >= open_ms else "open"
+        dom_ms, dom_alg = (seal_ms, seal_alg) if dominant == "seal" else (open_ms, open_alg)
+        achieved = dom_alg / (dom_ms / 1e3) / 1e9
+        pmc = load_traffic(workload)
+        traffic = None
+        # only counters of the kernel family this run used (a kernel change makes them stale)
+        if pmc and pmc.get(dominant) and pmc[dominant].get("family") == eng.last_kernel():
+            traffic = pmc[dominant].get("hbm_bytes_per_launch")
+            n_pmc = pmc[dominant].get("packets_per_launch")
+            if traffic and n_pmc and n_pmc != w.n:
+                # counters taken on another shard size of the same geometry (config 5 on one GPU vs a rank's
+                # shard): HBM bytes per packet carried over
+                traffic = int(round(traffic * w.n / n_pmc))
+
+        out.update({
+            "seal_ms": round(seal_ms, 5),
+            "open_ms": round(open_ms, 5),
+            "seal_ms_median": round(seal_each[reps // 2], 5),  # the median beside the mean
+            "open_ms_median": round(open_each[reps // 2], 5),
+            "seal_gib_s": round(payload / (seal_ms / 1e3) / 2**30 * world, 3),
+            "open_gib_s": round(payload / (open_ms / 1e3) / 2**30 * world, 3),
+            "seal_mpkt_s": round(w.n / (seal_ms / 1e3) / 1e6 * world, 3),
+        })
+        ceil_gbs = valu_ceiling_gbs(w.desc["len"], False)
+        out["roofline"], out["valu_roofline"] = rooflines(dominant, achieved, dom_alg, traffic,
+                                                          payload / (seal_ms / 1e3) / 1e9, ceil_gbs,
+                                                          KERNEL_CLOCK_GHZ.get(workload))
+        if pmc:
+            out["roofline"]["pmc_source"] = pmc.get("source")
+        if copy_ceiling:
+            # the spec peak stays the denominator; the copy rate is what a plain streaming kernel reaches here
+            out["roofline"]["copy_achievable"] = copy_ceiling
+            out["roofline"]["frac_of_copy"] = round(achieved / copy_ceiling["gb_s"], 4)
+        if cold:
+            # the cold-cache leg's own HBM roofline fraction (the step above runs on a cache-resident batch)
+            cold_dom_ms = cold["seal_ms"] if dominant == "seal" else cold["open_ms"]
+            cold["roofline"] = {"kernel": dominant, "achieved": round(dom_alg / (cold_dom_ms / 1e3) / 1e9, 2),
+                                "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(dom_alg / (cold_dom_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+            cold["vs_warm"] = {"seal": round(cold["seal_ms"] / seal_ms, 3), "open": round(cold["open_ms"] / open_ms, 3),
+                               "gib_s": round(cold["gib_s"] / (2 * payload / ((seal_ms + open_ms) / 1e3) / 2**30), 3)}
+            out["cold_cache"] = cold
     if forged:
         out["forged_open"] = forged
     # the host path (never `value`), on request: its 8 MiB slice launches would otherwise sit in a rocprofv3

@@ -23,24 +23,38 @@ def _run(args, env_extra=None, timeout=240):
 
 
 def test_gpus_n_launches_n_ranks():
-    r = _run(["--gpus", "2", "--dry-run"])
+    r = _run(["--gpus", "2", "--dry-run", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert sorted(x["rank"] for x in lines) == [0, 1]
     assert all(x["world"] == 2 and x["gpus"] == 2 and x["workload"] == "cfg5" for x in lines)
     assert sorted(x["local_rank"] for x in lines) == [0, 1]
-    # the N > 1 line is self-contained: rank 0 also runs the same workload's 1-GPU base and the CPU baselines
+    # the N > 1 --full line is self-contained: rank 0 also runs the same workload's 1-GPU base and the CPU baselines
     legs = {x["rank"]: x["legs"] for x in lines}
     assert legs[0] == ["timed", "base_1gpu", "single_process", "e2e_multi", "cpu_baseline"] and legs[1] == ["timed"]
 
 
-def test_single_gpu_defaults_to_cfg2():
+def test_plain_run_plans_the_timed_steps_only():
+    """Without --full no rank plans anything beside the timed steps, whatever the legs' own options say."""
+    r = _run(["--gpus", "2", "--dry-run", "--cpu-seconds", "5", "--forged", "0.5"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert sorted(x["rank"] for x in lines) == [0, 1]
+    assert all(x["legs"] == ["timed"] and x["forged"] == [] for x in lines)
     r = _run(["--dry-run"])
+    (line,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert line == {"rank": 0, "world": 1, "gpus": 1, "local_rank": 0, "workload": "cfg2", "forged": []}
+    r = _run(["--dry-run", "--e2e"])  # a --full leg asked for without --full
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_single_gpu_defaults_to_cfg2():
+    r = _run(["--dry-run", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     (line,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
-    # the default line also times the open with 1 % and 10 % forged tags (forged_open)
+    # the default --full line also times the open with 1 % and 10 % forged tags (VERDICT r2: forged_open)
     assert line == {"rank": 0, "world": 1, "gpus": 1, "local_rank": 0, "workload": "cfg2", "forged": [0.01, 0.1]}
-    r = _run(["--dry-run", "--forged", "0"])
+    r = _run(["--dry-run", "--full", "--forged", "0"])
     (line,) = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert line["forged"] == []
     r = _run(["--dry-run", "--forged", "1.5"])

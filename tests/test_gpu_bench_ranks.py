@@ -27,7 +27,8 @@ def test_torchrun_two_ranks_sharing_one_gpu():
     env = dict(os.environ, RG_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--forged", "0", "--no-cold"]
+           "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0", "--forged", "0",
+           "--no-cold"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]

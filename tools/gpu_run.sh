@@ -40,7 +40,7 @@ each_variant() { # callback name workload flags...
     done
 }
 
-bench_variant() { local n=$1 W=$2; shift 2; run var_$n 200 python bench.py --workload $W "$@" --steps 20 --warmup 3 --cpu-seconds 0; }
+bench_variant() { local n=$1 W=$2; shift 2; run var_$n 200 python bench.py --full --workload $W "$@" --steps 20 --warmup 3 --cpu-seconds 0; }
 stamp_variant() { local n=$1 W=$2; shift 2; run stv_$n 200 python tools/stamps.py --workload $W "$@"; }
 pmc_variant() {
     local n=$1 W=$2; shift 2
@@ -59,15 +59,15 @@ for s in "$@"; do
     test) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     testall) run pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread ;;
     ktest) run pytest_k 900 python -u -m pytest tests -m gpu -x -v -k "${PYTEST_K}" --timeout 180 --timeout-method thread ;;
-    bench) run bench 400 python bench.py --steps 50 --warmup 10 --cpu-seconds 10 ;;
-    benchq) run bench 300 python bench.py --steps 30 --warmup 5 --cpu-seconds 0 ;;
+    bench) run bench 400 python bench.py --full --steps 50 --warmup 10 --cpu-seconds 10 ;;
+    benchq) run bench 300 python bench.py --full --steps 30 --warmup 5 --cpu-seconds 0 ;;
     bench_all)
-        for w in ${RG_WORKLOADS:-cfg2 cfg3 cfg4 cfg5}; do run bench_$w 300 python bench.py --workload $w --steps 30 --warmup 5 --cpu-seconds 0; done
+        for w in ${RG_WORKLOADS:-cfg2 cfg3 cfg4 cfg5}; do run bench_$w 300 python bench.py --full --workload $w --steps 30 --warmup 5 --cpu-seconds 0; done
         summ gpurun_out/bench_cfg[2-5].log ;;
-    e2e) run e2e 400 python bench.py --steps 10 --warmup 3 --cpu-seconds 0 --e2e ;;
-    default) run bench_default 600 python bench.py ;;
+    e2e) run e2e 400 python bench.py --full --steps 10 --warmup 3 --cpu-seconds 0 --e2e ;;
+    default) run bench_default 600 python bench.py --full ;;
     defprof) run prof_default 700 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_default -o run -- \
-        python3 bench.py ;;
+        python3 bench.py --full ;;
     cfg1) run bench_cfg1 300 python bench.py --workload cfg1 ;;
     prof)
         W=${RG_WORKLOAD:-cfg2}

@@ -8,6 +8,7 @@ set -u
 SELF=$(readlink -f "$0")
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
+OUT=$_  # the output folder made above: the bench lines below write their logs there
 export TMPDIR=/tmp
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 
@@ -29,7 +30,7 @@ timeout -k 10 120 python tools/stamps.py --workload cfg2 --plan 0 > gpurun_out/d
 tail -n 30 gpurun_out/diag_stamps.log
 for v in "base:" "m1:--debug-mode 1 --no-verify" "m2:--debug-mode 2 --no-verify" "m8:--debug-mode 8 --no-verify" "l2:--lanes 2" "p0:--plan 0" "wg2:--wg-per-cu 2 --plan 0"; do
   n=${v%%:*}; f=${v#*:}
-  timeout -k 10 120 python bench.py --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > gpurun_out/diag_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > $OUT/diag_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/diag_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["config"]["kernel"][:50])')"
 done
 }
@@ -39,7 +40,7 @@ recipe_cfg2_diag2() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for v in "base:--plan 0" "m1:--debug-mode 1 --no-verify --plan 0" "m7:--debug-mode 7 --no-verify --plan 0" "l2:--lanes 2 --plan 0" "l2m1:--lanes 2 --debug-mode 1 --no-verify --plan 0" "l2m7:--lanes 2 --debug-mode 7 --no-verify --plan 0" "l4m1:--lanes 4 --debug-mode 1 --no-verify --plan 0"; do
   n=${v%%:*}; f=${v#*:}
-  timeout -k 10 120 python bench.py --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > gpurun_out/diag2_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > $OUT/diag2_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/diag2_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["config"]["kernel"][:50])')"
 done
 for m in 1 7 0; do
@@ -55,7 +56,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 300 bash tools/ab.sh "base lf1 d4 d4lf" "cfg2" 3 --no-cold || exit $?
 for v in "l2w2:--lanes 2 --wg-per-cu 2 --plan 0" "l2w2m1:--lanes 2 --wg-per-cu 2 --plan 0 --debug-mode 1 --no-verify" "l2w2m7:--lanes 2 --wg-per-cu 2 --plan 0 --debug-mode 7 --no-verify" "l4w4:--lanes 4 --wg-per-cu 4 --plan 0"; do
   n=${v%%:*}; f=${v#*:}
-  timeout -k 10 120 python bench.py --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > gpurun_out/diag3_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > $OUT/diag3_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/diag3_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["config"]["kernel"][:50])')"
 done
 export RG_AEAD_LIB=tools/build/librg_d4lf.so
@@ -67,7 +68,7 @@ recipe_cfg2_storecost() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for v in "base:" "m8:--debug-mode 8 --no-verify" "m7:--debug-mode 7 --no-verify"; do
   n=${v%%:*}; f=${v#*:}
-  timeout -k 10 120 python bench.py --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --plan 0 $f > gpurun_out/sc_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --plan 0 $f > $OUT/sc_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/sc_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"])')"
 done
 timeout -k 10 120 python tools/stamps.py --workload cfg2 --plan 0 --mode 8 > gpurun_out/sc_stamps_m8.log 2>&1 || exit $?
@@ -82,7 +83,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for v in "auto:" "t1s1:--staged 1 --segments 1" "t1s2:--staged 1 --segments 2" "t2s1:--staged 2 --segments 1" "t2s2:--staged 2 --segments 2" "t2s4:--staged 2 --segments 4" "t1s4:--staged 1 --segments 4" "c4auto:--workload cfg4" "c4t2s2:--workload cfg4 --staged 2 --segments 2"; do
   n=${v%%:*}; f=${v#*:}
   w=cfg2; case "$f" in *cfg4*) w=cfg4; f=${f/--workload cfg4/};; esac
-  timeout -k 10 120 python bench.py --workload $w --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > gpurun_out/tiles_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload $w --steps 20 --warmup 3 --cpu-seconds 0 --no-cold $f > $OUT/tiles_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/tiles_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["config"]["kernel"][:60])')"
 done
 }
@@ -102,7 +103,7 @@ recipe_cfg3_stamps() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 120 python tools/flat_stamps.py --workload cfg3 > gpurun_out/flat_stamps.log 2>&1 || exit $?
 cat gpurun_out/flat_stamps.log | grep -v amdgpu.ids
-timeout -k 10 120 python bench.py --workload cfg3 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > gpurun_out/cfg3_bench.log 2>&1 || exit $?
+timeout -k 10 120 python bench.py --full --workload cfg3 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > $OUT/cfg3_bench.log 2>&1 || exit $?
 grep '^{' gpurun_out/cfg3_bench.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"])'
 }
 
@@ -111,7 +112,7 @@ recipe_cfg3_tiles() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for v in "auto:" "t2:--staged 2" "t1:--staged 1" "t2s1:--staged 2 --segments 1" "t2s2:--staged 2 --segments 2" "pipe:--staged 0"; do
   n=${v%%:*}; f=${v#*:}
-  timeout -k 10 120 python bench.py --workload cfg3 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --forged 0 $f > gpurun_out/c3t_$n.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg3 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --forged 0 $f > $OUT/c3t_$n.log 2>&1 || exit $?
   echo "$n $(grep '^{' gpurun_out/c3t_$n.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["config"]["kernel"][:60])')"
 done
 }
@@ -128,8 +129,8 @@ recipe_check_bench() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || exit $?
 tail -n 1 gpurun_out/smoke.log
-timeout -k 10 200 python bench.py --steps 20 --warmup 3 --cpu-seconds 0 > gpurun_out/chk_cfg2.log 2>&1 || exit $?
-timeout -k 10 200 python bench.py --workload cfg5 --steps 5 --warmup 2 --cpu-seconds 0 > gpurun_out/chk_cfg5.log 2>&1 || exit $?
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 > $OUT/chk_cfg2.log 2>&1 || exit $?
+timeout -k 10 200 python bench.py --full --workload cfg5 --steps 5 --warmup 2 --cpu-seconds 0 > $OUT/chk_cfg5.log 2>&1 || exit $?
 for f in gpurun_out/chk_cfg2.log gpurun_out/chk_cfg5.log; do grep '^{' $f | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["wire_gib_s"], d["roofline"])'; done
 }
 
@@ -162,7 +163,7 @@ recipe_forged() {
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for v in "cfg2:0.1" "cfg2:1.0" "cfg4:0.1" "cfg4:1.0"; do
   w=${v%%:*}; f=${v#*:}
-  timeout -k 10 200 python bench.py --workload $w --steps 10 --warmup 2 --cpu-seconds 0 --no-cold --forged $f > gpurun_out/forged_${w}_$f.log 2>&1 || exit $?
+  timeout -k 10 200 python bench.py --full --workload $w --steps 10 --warmup 2 --cpu-seconds 0 --no-cold --forged $f > $OUT/forged_${w}_$f.log 2>&1 || exit $?
   echo "$w $f $(grep '^{' gpurun_out/forged_${w}_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
 }
@@ -230,10 +231,10 @@ RG_AEAD_LIB=tools/build/librg_nodma.so timeout -k 10 120 python tools/stamps.py 
 grep -A3 '"seal"\|"open"' gpurun_out/r3_stamps_dma.log gpurun_out/r3_stamps_nodma.log | grep -v "^--$" | head -20
 tools/ab.sh "base nodma d3 d6" "cfg2" 2 --no-cold || exit $?
 for f in 0.01 0.1; do
-  timeout -k 10 120 python bench.py --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3_forged_$f.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3_forged_$f.log 2>&1 || exit $?
   echo "forged $f $(grep '^{' gpurun_out/r3_forged_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
-timeout -k 10 120 python bench.py --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged 0.1 > gpurun_out/r3_forged_cfg4.log 2>&1 || exit $?
+timeout -k 10 120 python bench.py --full --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged 0.1 > $OUT/r3_forged_cfg4.log 2>&1 || exit $?
 echo "cfg4 forged 0.1 $(grep '^{' gpurun_out/r3_forged_cfg4.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 }
 
@@ -244,7 +245,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-me
 rc=$?; tail -2 gpurun_out/final_gpu.log; [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/final_smoke.log 2>&1 || exit $?
 tail -1 gpurun_out/final_smoke.log
-timeout -k 10 400 python bench.py > gpurun_out/final_bench.log 2>&1 || exit $?
+timeout -k 10 400 python bench.py --full > $OUT/final_bench.log 2>&1 || exit $?
 grep '^{' gpurun_out/final_bench.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["seal_ms"], d["open_ms"], d["roofline"]["frac"], d["valu_roofline"]["frac"], [f["ratio"] for f in d["forged_open"]])'
 }
 
@@ -255,7 +256,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_forged.py tests/test_gpu_pa
 tail -n 3 gpurun_out/r3_flat_tests.log
 [ $rc -eq 0 ] || exit $rc
 for f in 0.01 0.1 1.0; do
-  timeout -k 10 150 python bench.py --workload cfg3 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3f_cfg3_$f.log 2>&1 || exit $?
+  timeout -k 10 150 python bench.py --full --workload cfg3 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3f_cfg3_$f.log 2>&1 || exit $?
   echo "cfg3 $f $(grep '^{' gpurun_out/r3f_cfg3_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
 }
@@ -283,7 +284,7 @@ for lib in base mf; do
   if [ $lib = base ]; then unset RG_AEAD_LIB; else export RG_AEAD_LIB=tools/build/librg_$lib.so; fi
   for w in cfg2 cfg3 cfg4; do
     for f in 0.01 0.1 1.0; do
-      timeout -k 10 150 python bench.py --workload $w --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3f_${lib}_${w}_$f.log 2>&1 || exit $?
+      timeout -k 10 150 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3f_${lib}_${w}_$f.log 2>&1 || exit $?
       echo "$lib $w $f $(grep '^{' gpurun_out/r3f_${lib}_${w}_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
     done
   done
@@ -310,7 +311,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_forged.py tests/test_gpu_pa
 tail -n 3 gpurun_out/r3_mf_tests.log
 [ $rc -eq 0 ] || exit $rc
 for f in 0.01 0.1 1.0; do
-  timeout -k 10 120 python bench.py --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3_forged_$f.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3_forged_$f.log 2>&1 || exit $?
   echo "cfg2 forged $f $(grep '^{' gpurun_out/r3_forged_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
 tools/ab.sh "base df stag16 stag32" "cfg2" 3 --no-cold || exit $?
@@ -374,7 +375,7 @@ recipe_r3_rehearse() {
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 120 --timeout-method thread > gpurun_out/allgpu.log 2>&1
 rc=$?; tail -2 gpurun_out/allgpu.log; [ $rc -ne 0 ] && exit $rc
-RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 > gpurun_out/rehearse2.log 2>&1
+RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --full --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 > $OUT/rehearse2.log 2>&1
 rc=$?; tail -c 3000 gpurun_out/rehearse2.log; exit $rc
 }
 
@@ -384,7 +385,7 @@ recipe_r3_rehearse_torchrun() {
 cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 for n in 2 4; do
   RG_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 5 --warmup 2 --cpu-seconds 2 \
+    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $n --steps 5 --warmup 2 --cpu-seconds 2 \
     > gpurun_out/rehearse_tr$n.log 2>&1
   rc=$?; grep '^{' gpurun_out/rehearse_tr$n.log | cut -c1-400; [ $rc -ne 0 ] && { tail -20 gpurun_out/rehearse_tr$n.log; exit $rc; }
 done
@@ -409,11 +410,11 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_forged.py -x -q --timeout 1
 tail -n 3 gpurun_out/r3_forged_tests.log
 [ $rc -le 1 ] || exit $rc
 for f in 0.01 0.1 1.0; do
-  timeout -k 10 120 python bench.py --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3_forged_$f.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3_forged_$f.log 2>&1 || exit $?
   echo "cfg2 forged $f $(grep '^{' gpurun_out/r3_forged_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
 for f in 0.01 0.1; do
-  timeout -k 10 120 python bench.py --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > gpurun_out/r3_forged_cfg4_$f.log 2>&1 || exit $?
+  timeout -k 10 120 python bench.py --full --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged $f > $OUT/r3_forged_cfg4_$f.log 2>&1 || exit $?
   echo "cfg4 forged $f $(grep '^{' gpurun_out/r3_forged_cfg4_$f.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["open_ms"], d["forged_open"])')"
 done
 tools/ab.sh "base spread wt3 stag16 stag5" "cfg2" 2 --no-cold || exit $?
@@ -491,7 +492,7 @@ rc=$?
 tail -2 gpurun_out/r4_check2_gputest.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/r4_check2_smoke.log 2>&1 && tail -1 gpurun_out/r4_check2_smoke.log &&
-timeout -k 10 400 python bench.py --e2e > gpurun_out/r4_check2_default.jsonl 2> gpurun_out/r4_check2_default.err && cut -c1-300 gpurun_out/r4_check2_default.jsonl
+timeout -k 10 400 python bench.py --full --e2e > $OUT/r4_check2_default.jsonl 2> $OUT/r4_check2_default.err && cut -c1-300 $OUT/r4_check2_default.jsonl
 }
 
 recipe_r4_check3() {
@@ -501,7 +502,7 @@ rc=$?
 tail -2 gpurun_out/r4_check3_gputest.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/r4_check3_smoke.log 2>&1 && tail -1 gpurun_out/r4_check3_smoke.log &&
-timeout -k 10 400 python bench.py --e2e > gpurun_out/r4_check3_default.jsonl 2> gpurun_out/r4_check3_default.err && cut -c1-300 gpurun_out/r4_check3_default.jsonl
+timeout -k 10 400 python bench.py --full --e2e > $OUT/r4_check3_default.jsonl 2> $OUT/r4_check3_default.err && cut -c1-300 $OUT/r4_check3_default.jsonl
 }
 
 recipe_r4_cores() {
@@ -517,7 +518,7 @@ timeout -k 10 120 python tools/coresidency.py --lanes 1 --wg-per-cu 1 --mode 1 >
 recipe_r4_default() {
 # Round 4: the default bench line exactly as the driver runs it (no flags; the host path now on by default).
 t0=$(date +%s)
-timeout -k 10 400 python bench.py > gpurun_out/r4_default_noflags.jsonl 2> gpurun_out/r4_default_noflags.err
+timeout -k 10 400 python bench.py --full > $OUT/r4_default_noflags.jsonl 2> $OUT/r4_default_noflags.err
 rc=$?
 echo "wall $(( $(date +%s) - t0 )) s, rc $rc"
 python3 -c "import json; d=json.loads(open('gpurun_out/r4_default_noflags.jsonl').read().strip().splitlines()[-1]); print(d['value'], d.get('e2e'))"
@@ -526,7 +527,7 @@ exit $rc
 
 recipe_r4_defprof() {
 # Round 4: rocprofv3 kernel stats of the default bench command itself (python bench.py, no flags).
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_default -o run -- python3 bench.py > gpurun_out/prof_default.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_default -o run -- python3 bench.py --full > $OUT/prof_default.log 2>&1
 rc=$?
 grep '^{' gpurun_out/prof_default.log | cut -c1-200
 find gpurun_out/prof_default -name "*kernel_stats.csv" | head -2
@@ -621,9 +622,9 @@ rc=$?
 tail -2 gpurun_out/r4_gputest.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python tools/e2e_probe.py cfg2 8,16,32 > gpurun_out/r4_e2e_probe3.jsonl && cat gpurun_out/r4_e2e_probe3.jsonl &&
-timeout -k 10 400 python bench.py --e2e > gpurun_out/r4_bench_default.jsonl 2> gpurun_out/r4_bench_default.err && cat gpurun_out/r4_bench_default.jsonl &&
-RG_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --single-process --gpus 2 --steps 5 --warmup 2 > gpurun_out/r4_single_share2.jsonl 2> gpurun_out/r4_single_share2.err && cat gpurun_out/r4_single_share2.jsonl &&
-RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 > gpurun_out/r4_rehearse_torchrun2.jsonl 2> gpurun_out/r4_rehearse_torchrun2.err && cat gpurun_out/r4_rehearse_torchrun2.jsonl
+timeout -k 10 400 python bench.py --full --e2e > $OUT/r4_bench_default.jsonl 2> $OUT/r4_bench_default.err && cat $OUT/r4_bench_default.jsonl &&
+RG_BENCH_SHARE_GPU=1 timeout -k 10 300 python bench.py --full --single-process --gpus 2 --steps 5 --warmup 2 > $OUT/r4_single_share2.jsonl 2> $OUT/r4_single_share2.err && cat $OUT/r4_single_share2.jsonl &&
+RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 > $OUT/r4_rehearse_torchrun2.jsonl 2> $OUT/r4_rehearse_torchrun2.err && cat $OUT/r4_rehearse_torchrun2.jsonl
 RG_AEAD_LIB=tools/build/librg_diag.so timeout -k 10 200 python tools/flat_stamps.py --workload cfg3 > gpurun_out/r4_cfg3_flat_stamps.txt 2>&1 && cat gpurun_out/r4_cfg3_flat_stamps.txt
 }
 
@@ -700,8 +701,8 @@ cat gpurun_out/icache_summary.txt
 recipe_r4_last() {
 # Round 4, last measurement on the final build: the default bench line with the host path, and the N = 4
 # launcher path as the driver runs it with the four ranks sharing the GPU (RG_BENCH_SHARE_GPU=1).
-timeout -k 10 400 python bench.py --e2e > gpurun_out/r4_last_default.jsonl 2> gpurun_out/r4_last_default.err && cat gpurun_out/r4_last_default.jsonl | cut -c1-600 &&
-RG_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 4 --steps 5 --warmup 2 --cpu-seconds 2 > gpurun_out/r4_rehearse_torchrun4.jsonl 2> gpurun_out/r4_rehearse_torchrun4.err && cut -c1-400 gpurun_out/r4_rehearse_torchrun4.jsonl
+timeout -k 10 400 python bench.py --full --e2e > $OUT/r4_last_default.jsonl 2> $OUT/r4_last_default.err && cat $OUT/r4_last_default.jsonl | cut -c1-600 &&
+RG_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 4 --steps 5 --warmup 2 --cpu-seconds 2 > $OUT/r4_rehearse_torchrun4.jsonl 2> $OUT/r4_rehearse_torchrun4.err && cut -c1-400 $OUT/r4_rehearse_torchrun4.jsonl
 }
 
 recipe_r4_lb2() {
@@ -712,7 +713,7 @@ run() { # name lib flags...
     local name=$1 lib=$2
     shift 2
     if [ "$lib" = base ]; then unset RG_AEAD_LIB; else export RG_AEAD_LIB=tools/build/librg_$lib.so; fi
-    timeout -k 10 200 python bench.py --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --forged 0 "$@" \
+    timeout -k 10 200 python bench.py --full --workload cfg2 --steps 20 --warmup 3 --cpu-seconds 0 --no-cold --forged 0 "$@" \
         >gpurun_out/r4lb2_$name.log 2>&1 || { echo "$name FAILED $?"; tail -5 gpurun_out/r4lb2_$name.log; exit 1; }
     python3 -c "import json; d=json.loads([l for l in open('gpurun_out/r4lb2_$name.log') if l.startswith('{')][-1]); print('$name', d['value'], d['seal_ms'], d['open_ms'], d['config']['kernel'][:40])"
 }
@@ -761,7 +762,7 @@ bash tools/ab.sh "base head" "cfg3" 4 --no-cold --forged 0 2>&1 | tee gpurun_out
 
 recipe_r4_pcie2() {
 # Round 4: the bench line's e2e.pcie_ceiling with hipHostMalloc buffers (short bench run).
-timeout -k 10 300 python bench.py --e2e --steps 5 --warmup 2 --cpu-seconds 0 --forged 0 --no-cold > gpurun_out/r4_pcie2.jsonl 2>gpurun_out/r4_pcie2.err && python3 -c "import json; d=json.loads(open('gpurun_out/r4_pcie2.jsonl').read()); print(d['e2e'])"
+timeout -k 10 300 python bench.py --full --e2e --steps 5 --warmup 2 --cpu-seconds 0 --forged 0 --no-cold > $OUT/r4_pcie2.jsonl 2>$OUT/r4_pcie2.err && python3 -c "import json; d=json.loads(open('$OUT/r4_pcie2.jsonl').read()); print(d['e2e'])"
 }
 
 recipe_r4_perwave() {
@@ -921,7 +922,7 @@ recipe_r5_a() {
 cd $GRAFT_REPO_ROOT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 bash tools/gpu_run.sh test && \
-RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --single-process --gpus 2 --steps 5 --warmup 2 > gpurun_out/sp2.log 2>&1; echo rc=$?; tail -c 3000 gpurun_out/sp2.log
+RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --full --single-process --gpus 2 --steps 5 --warmup 2 > $OUT/sp2.log 2>&1; echo rc=$?; tail -c 3000 $OUT/sp2.log
 }
 
 recipe_r5_e2eenv() {
@@ -999,7 +1000,7 @@ recipe_ab_lib() {
 for rep in 1 2; do
     for v in ${LIBS:-base}; do
         if [ $v = base ]; then L=""; else L="RG_AEAD_LIB=tools/build/librg_$v.so"; fi
-        env $L timeout -k 10 200 python bench.py --workload ${W:-cfg3} ${FLAGS:-} --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > gpurun_out/ab_${v}_$rep.log 2>&1 || exit 1
+        env $L timeout -k 10 200 python bench.py --full --workload ${W:-cfg3} ${FLAGS:-} --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > $OUT/ab_${v}_$rep.log 2>&1 || exit 1
         python3 -c "import json; d=json.loads([l for l in open('gpurun_out/ab_${v}_$rep.log') if l.startswith('{')][-1]); print('$v', $rep, d['value'], d['seal_ms'], d['open_ms'])"
     done
 done
@@ -1011,7 +1012,7 @@ for rep in 1 2; do
 for v in new old; do
   for sh in 0 112; do
     if [ $v = old ]; then L="RG_AEAD_LIB=tools/build/librg_oldtile.so"; else L=""; fi
-    env $L timeout -k 10 200 python bench.py --workload cfg4 --frame-shift $sh --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > gpurun_out/ab_${v}_${sh}_$rep.log 2>&1
+    env $L timeout -k 10 200 python bench.py --full --workload cfg4 --frame-shift $sh --steps 20 --warmup 3 --cpu-seconds 0 --no-cold > $OUT/ab_${v}_${sh}_$rep.log 2>&1
     python3 -c "import json,sys; d=json.loads([l for l in open('gpurun_out/ab_${v}_${sh}_$rep.log') if l.startswith('{')][-1]); print('$v', $sh, $rep, d['value'], d['seal_ms'], d['open_ms'])"
   done
 done
@@ -1043,12 +1044,12 @@ for s in "$@"; do
     forged) step forged 600 python -u -m pytest tests/test_gpu_forged.py -x -v --timeout 120 --timeout-method thread ;;
     parity) step parity 900 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_sessions.py tests/test_gpu_sessions_dev.py -v --timeout 120 --timeout-method thread ;;
     allgpu) step allgpu 1000 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread ;;
-    bench) step bench 300 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 ;;
-    bench_forged) step bench_forged 300 python bench.py --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged 0.1 ;;
-    bench_forged1) step bench_forged1 300 python bench.py --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged 0.01 ;;
-    bench_cfg4f) step bench_cfg4f 300 python bench.py --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged 0.1 ;;
-    bench_all) for w in cfg2 cfg3 cfg4 cfg5; do step bench_$w 300 python bench.py --workload $w --steps 10 --warmup 3 --no-cold --cpu-seconds 0; done ;;
-    prof) step prof 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run -- python bench.py --steps 20 --warmup 5 --no-cold --cpu-seconds 0 ;;
+    bench) step bench 300 python bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 ;;
+    bench_forged) step bench_forged 300 python bench.py --full --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged 0.1 ;;
+    bench_forged1) step bench_forged1 300 python bench.py --full --steps 10 --warmup 3 --no-cold --cpu-seconds 0 --forged 0.01 ;;
+    bench_cfg4f) step bench_cfg4f 300 python bench.py --full --workload cfg4 --steps 5 --warmup 2 --no-cold --cpu-seconds 0 --forged 0.1 ;;
+    bench_all) for w in cfg2 cfg3 cfg4 cfg5; do step bench_$w 300 python bench.py --full --workload $w --steps 10 --warmup 3 --no-cold --cpu-seconds 0; done ;;
+    prof) step prof 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python bench.py --full --steps 20 --warmup 5 --no-cold --cpu-seconds 0 ;;
     esac
 done
 }
@@ -1183,10 +1184,10 @@ recipe_r5_check() {
 # the N = 2 launcher path rehearsed on one GPU (torch.distributed.run, two ranks sharing the GPU over gloo;
 # its line now carries e2e_multi).
 bash tools/gpu_run.sh test smoke || return $?
-timeout -k 10 600 python bench.py > gpurun_out/r5_default.jsonl 2> gpurun_out/r5_default.err || { tail -5 gpurun_out/r5_default.err; return 1; }
+timeout -k 10 600 python bench.py --full > $OUT/r5_default.jsonl 2> $OUT/r5_default.err || { tail -5 $OUT/r5_default.err; return 1; }
 cut -c1-600 gpurun_out/r5_default.jsonl
 RG_BENCH_SHARE_GPU=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 \
+    --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 5 --warmup 2 --cpu-seconds 2 \
     > gpurun_out/r5_rehearse_tr2.log 2>&1
 rc=$?; grep '^{' gpurun_out/r5_rehearse_tr2.log | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d.get('speedup'), json.dumps(d.get('e2e_multi'))[:800])"
 [ $rc -ne 0 ] && { tail -20 gpurun_out/r5_rehearse_tr2.log; return $rc; }
@@ -1247,7 +1248,7 @@ RG_WORKLOADS=cfg3 bash tools/gpu_run.sh valu bench_all || return $?
 for v in base gthr0; do
     for n in 2 4; do
         if [ $v = base ]; then unset RG_AEAD_LIB; else export RG_AEAD_LIB=tools/build/librg_$v.so; fi
-        RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --single-process --gpus $n --steps 5 --warmup 2 \
+        RG_BENCH_SHARE_GPU=1 timeout -k 10 400 python bench.py --full --single-process --gpus $n --steps 5 --warmup 2 \
             --cpu-seconds 0 > gpurun_out/r5_gthr_${v}_$n.log 2>&1 || return $?
         grep '^{' gpurun_out/r5_gthr_${v}_$n.log | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', $n, json.dumps(d.get('e2e_multi'))[:700])"
     done
@@ -1372,7 +1373,7 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 gpurun_out/sched2_tests.log
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || return 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/sched2_prof -o run \
-    -- python3 bench.py > gpurun_out/sched2_default.jsonl 2> gpurun_out/sched2_default.err || { echo "prof rc=$?"; return 1; }
+    -- python3 bench.py --full > $OUT/sched2_default.jsonl 2> $OUT/sched2_default.err || { echo "prof rc=$?"; return 1; }
 grep -h "seal_kernel\|open_kernel" $(find gpurun_out/sched2_prof -name "*kernel_stats.csv") | cut -c1-160
 }
 
@@ -1438,7 +1439,7 @@ timeout -k 10 300 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 gpurun_out/rg_tests.log
 for r in 1 2; do for v in base prev; do
     if [ $v = base ]; then unset RG_AEAD_LIB; else export RG_AEAD_LIB=tools/build/librg_$v.so; fi
-    timeout -k 10 200 python bench.py --workload cfg2 --steps 10 --warmup 3 --cpu-seconds 0 --no-cold > gpurun_out/rg_${v}_$r.log 2>&1 || return 1
+    timeout -k 10 200 python bench.py --full --workload cfg2 --steps 10 --warmup 3 --cpu-seconds 0 --no-cold > $OUT/rg_${v}_$r.log 2>&1 || return 1
     echo "$v $r $(grep '"value"' gpurun_out/rg_${v}_$r.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], [(f["forged_frac"], f["open_ms"], f["clean_open_ms"], f["ratio"]) for f in d["forged_open"]])')"
 done; done
 unset RG_AEAD_LIB
