@@ -89,6 +89,8 @@ enum rg_pkt_status {
                                handshake path (lib.rs:622-624) */
     RG_PKT_PENDING = 6,     /* no verdict: the packet was never finished (the call failed, a device
                                error, or a batch still in flight).  Never an accept. */
+    RG_PKT_COOKIE = 7,      /* rg_cookie_reply_batch_dev: mac1 valid, mac2 missing or wrong while overloaded;
+                               a cookie reply was written for this message */
 };
 
 /* Statuses fail closed.  A packet reads RG_PKT_OK only after the kernel that processed it wrote that
@@ -180,6 +182,60 @@ int rg_open_batch_dev_rx(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys, const
 int rg_mac_verify_batch_dev(rg_ctx *ctx, const uint8_t *keys, uint32_t key_len, uint32_t nkeys, int which,
                             const rg_pkt_desc *desc, size_t n, const uint8_t *buf, size_t buf_len, uint8_t *status,
                             uint32_t *key_idx_out, void *stream);
+
+/* ------------------------------- under-load handshake filter (batch) */
+/* HasMac::verify with overload = true (rustyguard-crypto/src/lib.rs:114-140) followed by
+ * Sessions::write_cookie_message (rustyguard-core/src/lib.rs:517-540) for n handshake messages in one
+ * launch: mac1 under the server's mac1 key, then -- while overloaded -- mac2 under the message's own
+ * cookie = BLAKE2s-128(secret, source address) (CookieState::new_cookie, lib.rs:95-104), and for every
+ * message whose mac2 fails a sealed 64-byte CookieMessage.  All pointers are device memory; the call
+ * enqueues on `stream` and returns without waiting, like rg_mac_verify_batch_dev.  buf is never written.
+ * The call keeps nothing in the context: the two key-only BLAKE2s states are recomputed by every
+ * workgroup and live in LDS, so calls on one context may run on any streams.
+ *
+ * desc[i]: offset, len = whole message.  Per message, in this order:
+ *   offset % 16 != 0                                   RG_PKT_UNALIGNED
+ *   frame outside [buf, buf + buf_len), or len neither
+ *   148 (initiation) nor 92 (response)                 RG_PKT_INVALID
+ *   key_idx == RG_KEY_SKIP                             RG_PKT_REJECTED, nothing read (any other key_idx
+ *                                                      is ignored)
+ *   type word != 1 for len 148 / != 2 for len 92       RG_PKT_INVALID (Error::InvalidMessage)
+ *   mac1 = BLAKE2s-128(mac1_key, msg[..len-32]) differs
+ *   from msg[len-32..len-16]                           RG_PKT_REJECTED, whatever mac2 says
+ *   overload && overload[i] == 0                       RG_PKT_OK
+ *   mac2 = BLAKE2s-128(cookie, msg[..len-16]) equals
+ *   msg[len-16..]                                      RG_PKT_OK: on to the handshake
+ *   otherwise                                          RG_PKT_COOKIE and replies[i] =
+ *       le32(3) || msg.sender (bytes 4..8) || nonces[i] || ct(16) || tag(16), with (ct, tag) =
+ *       XChaCha20-Poly1305(cookie_key, nonces[i], aad = the message's mac1 field, pt = cookie)
+ *       (encrypt_cookie, rustyguard-crypto/src/lib.rs:61-70).
+ * Reply rows of messages with any other status are not touched.  Statuses fail closed: the lane that
+ * judged a message writes its status, after its reply stores.
+ *
+ * Randomness: the library has no RNG.  nonces[i] must be 24 fresh bytes of the caller's CSPRNG for
+ * every message of every call (the reference draws them from its session RNG, rustyguard-core/src/
+ * lib.rs:529-530); their uniqueness and unpredictability are the caller's responsibility.  secret is
+ * CookieState.key, which the caller also rotates (lib.rs:79-93).
+ *
+ * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null pointer (overload may be NULL = all
+ * overloaded), n > 2^32 - 1, keys or replies not 16-byte aligned, addrs or nonces not 8-byte aligned. */
+typedef struct rg_cookie_keys {      /* device memory, 16-byte aligned, 96 bytes */
+    uint8_t mac1_key[32];            /* mac1_key(own static public key), lib.rs:72-74 */
+    uint8_t cookie_key[32];          /* cookie_key(own static public key), lib.rs:75-77: the XChaCha key */
+    uint8_t secret[32];              /* CookieState.key, rotated by the caller (lib.rs:79-93) */
+} rg_cookie_keys;
+
+typedef struct rg_src_addr {         /* 24 bytes, 8-byte aligned; CookieState::new_cookie's encoding */
+    uint8_t ip[16];                  /* IPv4: octets in ip[0..4], rest zero; IPv6: 16 octets */
+    uint16_t port_le;                /* little-endian port */
+    uint8_t pad[6];                  /* ignored: only the first 18 bytes are hashed */
+} rg_src_addr;
+
+int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys, const rg_pkt_desc *desc,
+                              const rg_src_addr *addrs, const uint8_t *overload /* [n] or NULL = all overloaded */,
+                              const uint8_t *nonces /* [n][24], caller's CSPRNG output */, size_t n,
+                              const uint8_t *buf, size_t buf_len, uint8_t *replies /* [n][64], 16-byte aligned */,
+                              uint8_t *status, void *stream);
 
 /* Tuning knobs.  lanes: lanes cooperating on one packet (0 = automatic, else
  * 1/2/4).  wg_per_cu: resident 256-thread workgroups per CU of the persistent

@@ -10,6 +10,9 @@ Reference interface -> this module
   AntiReplay {would_accept, mark_seen}    (anti_replay.rs:25-64) -> AntiReplay
   CryptoError::{DecryptionError, Rejected} (rustyguard-crypto/src/lib.rs:43-48)
                                          -> DecryptionError / Rejected exceptions
+  HasMac::verify (overload) + Sessions::write_cookie_message
+    (rustyguard-crypto/src/lib.rs:114-140, rustyguard-core/src/lib.rs:517-540)
+                                         -> Engine.cookie_reply_dev, encode_src_addr
   batched hot path                        -> Engine.seal_dev/open_dev (device
                                              tensors), seal_host/open_host (numpy)
   Sessions send/recv of data frames       -> Sessions.send_batch / recv_batch
@@ -27,6 +30,7 @@ from ._lib import check, lib
 from .workloads import DESC_DTYPE
 
 PKT_OK, PKT_DECRYPT_ERR, PKT_INVALID, PKT_REJECTED, PKT_UNALIGNED, PKT_NOT_DATA, PKT_PENDING = range(7)
+PKT_COOKIE = 7  # rg_cookie_reply_batch_dev: a cookie reply was written for this message
 RECV_AUTHENTICATED, RECV_KEEPALIVE = 1, 2
 KEY_SCAN = 0xFFFFFFFE  # rg_mac_verify_batch_dev: try every key
 KEY_SKIP = 0xFFFFFFFF
@@ -202,6 +206,21 @@ class Engine:
                                               _nbytes(buf), _vp(status), _vp(key_idx_out), _stream_handle(stream)),
               "rg_mac_verify_batch_dev")
 
+    def cookie_reply_dev(self, keys, desc, addrs, overload, nonces, buf, replies, status, stream=None):
+        """HasMac::verify under load plus Sessions::write_cookie_message for a batch of handshake messages
+        (rg_cookie_reply_batch_dev): keys = one rg_cookie_keys (96 bytes: mac1_key, cookie_key, secret), addrs =
+        encode_src_addr rows (24 bytes each), overload = one byte per message or None (all overloaded), nonces
+        = 24 bytes per message from the caller's CSPRNG, replies = 64 bytes per message.  status: PKT_OK (on to
+        the handshake), PKT_COOKIE (replies[i] holds the CookieMessage to send back), PKT_REJECTED (mac1),
+        PKT_INVALID, PKT_UNALIGNED."""
+        n = _ndesc(desc)
+        assert _nbytes(keys) == 96 and _nbytes(addrs) >= 24 * n and _nbytes(nonces) >= 24 * n
+        assert _nbytes(replies) >= 64 * n and _nbytes(status) >= n and (overload is None or _nbytes(overload) >= n)
+        self._check(self._L.rg_cookie_reply_batch_dev(self._h, _vp(keys), _vp(desc), _vp(addrs), _vp(overload),
+                                                      _vp(nonces), n, _vp(buf), _nbytes(buf), _vp(replies),
+                                                      _vp(status), _stream_handle(stream)),
+                    "rg_cookie_reply_batch_dev")
+
     def synth_fill_dev(self, desc, inner_len, buf, seed: int, stream=None):
         n = _ndesc(desc)
         self._check(self._L.rg_synth_fill_dev(self._h, _vp(desc), _vp(inner_len), n, _vp(buf), _nbytes(buf), seed,
@@ -265,6 +284,17 @@ class Engine:
                                                    else None, len(payload), _vp(t)), "rg_chacha20poly1305_dec")
         if rc == PKT_DECRYPT_ERR:
             raise DecryptionError()
+
+
+def encode_src_addr(ip: str, port: int) -> bytes:
+    """One rg_src_addr row (24 bytes) for Engine.cookie_reply_dev: CookieState::new_cookie's encoding of a
+    socket address (rustyguard-crypto/src/lib.rs:95-103) -- an IPv4 address's 4 octets or an IPv6 address's
+    16 at the front of 16 bytes, the port little-endian behind them -- and 6 bytes of padding."""
+    import ipaddress
+
+    if not 0 <= port <= 0xFFFF:
+        raise ValueError(f"port {port} out of range")
+    return ipaddress.ip_address(ip).packed.ljust(16, b"\0") + port.to_bytes(2, "little") + bytes(6)
 
 
 def nonce(counter: int) -> bytes:

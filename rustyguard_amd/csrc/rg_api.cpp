@@ -459,16 +459,7 @@ struct rg_ctx {
 
 namespace {
 
-// The caller's current HIP device, put back on the way out: every entry point selects its context's
-// device (and a group call each of its contexts' in turn), while the caller -- a torch program, say --
-// keeps its own device selected.
-struct DeviceGuard {
-    int dev = -1;
-    DeviceGuard() { (void)hipGetDevice(&dev); }
-    ~DeviceGuard() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-};
+using rg::DeviceGuard; // rg_internal.h
 
 // The host NUMA node closest to a GPU, -1 if unknown.  HIP's attribute first; this runtime answers it with
 // hipErrorInvalidValue (round 6 box), and a failed query stays the thread's last error, which the next
@@ -537,6 +528,10 @@ void mark_stream(rg_ctx *ctx, hipStream_t st, hipEvent_t ev) {
 }
 
 } // namespace
+
+// rg_internal.h: the context as seen by entry points outside this file (rg_cookie.hip)
+int rg::ctx_select(rg_ctx *ctx) { return check_ctx(ctx); }
+int rg::api_error(int code, const char *what, hipError_t e) { return set_err(code, what, e); }
 
 extern "C" {
 

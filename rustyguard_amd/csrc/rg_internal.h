@@ -53,6 +53,27 @@ struct MacArgs {
 };
 hipError_t launch_mac_verify(const MacArgs &a, hipStream_t s);
 
+// An entry point that lives beside its kernel (rg_cookie_reply_batch_dev, rg_cookie.hip) reaches the
+// context through these two, defined in rg_api.cpp: rg_api.cpp itself then needs no launcher of that
+// kernel (it is also linked against a CPU stand-in for the launchers, tests/sanitize).
+// ctx_select: the null check and hipSetDevice of every entry point; RG_OK or the error, already recorded.
+int ctx_select(rg_ctx *ctx);
+// records the text rg_last_error() returns on this thread (with HIP's error string when e is one); returns code
+int api_error(int code, const char *what, hipError_t e = hipSuccess);
+
+// The caller's current HIP device, put back on the way out: every entry point selects its context's
+// device (and a group call each of its contexts' in turn), while the caller -- a torch program, say --
+// keeps its own device selected.
+struct DeviceGuard {
+    int dev = -1;
+    DeviceGuard() { (void)hipGetDevice(&dev); }
+    ~DeviceGuard() {
+        if (dev >= 0) (void)hipSetDevice(dev);
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
 // General AEAD job for the per-message drop-in (any nonce / AAD / length).
 struct GeneralJob {
     uint32_t key[8];

@@ -3,11 +3,15 @@
 
   mac1   rg_mac_verify_batch_dev: 1 Mi handshake-initiation messages (148 B), mac1 checked under the
          message's own key, and under an 8-peer scan (RG_KEY_SCAN, wg-proxy)
+  cookie rg_cookie_reply_batch_dev: 1 Mi initiations with a valid mac1 and no valid mac2, all overloaded, so
+         every message takes the whole path (mac1, cookie, mac2, sealed CookieMessage); beside it, in the
+         same run, rg_mac_verify_batch_dev (which = 1) on the same batch, and their ratio
   rx     rg_open_batch_dev_rx vs rg_open_batch_dev on config 4 frames (256 sessions): the cost of
          resolving every frame's session from its header on the device
 
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
-rejects, which costs the same as accepting)."""
+rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
+import hashlib
 import json
 import os
 import sys
@@ -34,10 +38,44 @@ def timed(fn, reps=20):
     return a.elapsed_time(b) / reps
 
 
-def main():
-    eng = aead.Engine(0)
-    out = {}
-    # ---------------------------------------------------------------- mac1
+def cookie_leg(eng, n=1 << 20):
+    L = 148
+    rng = np.random.default_rng(17)
+    ck = rng.integers(0, 256, 96, dtype=np.uint8)  # rg_cookie_keys: mac1_key, cookie_key, secret
+    mac1_key = ck[:32].tobytes()
+    host = rng.integers(0, 256, (n, 160), dtype=np.uint8)
+    host[:, 0:4] = (1, 0, 0, 0)  # HandshakeInit
+    host[:, L - 16:L] = 0        # no mac2
+    for row in host:             # a valid mac1: the reply path runs for every message
+        row[L - 32:L - 16] = np.frombuffer(hashlib.blake2s(row[:L - 32].tobytes(), key=mac1_key, digest_size=16).digest(),
+                                           np.uint8)
+    desc = np.zeros(n, DESC_DTYPE)
+    desc["offset"] = np.arange(n, dtype=np.uint64) * 160
+    desc["len"] = L
+    buf = torch.from_numpy(host.reshape(-1)).cuda()
+    d = torch.from_numpy(desc.view(np.uint8).reshape(-1, 16)).cuda()
+    keys = torch.from_numpy(ck).cuda()
+    addrs = torch.from_numpy(rng.integers(0, 256, (n, 24), dtype=np.uint8)).cuda()
+    nonces = torch.from_numpy(rng.integers(0, 256, (n, 24), dtype=np.uint8)).cuda()
+    replies = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+    st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    st1 = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    mac1_keys = keys[:32].clone()
+    # alternating repetitions, medians (the two calls are compared with each other)
+    t_cookie, t_mac1 = [], []
+    for _ in range(5):
+        t_cookie.append(timed(lambda: eng.cookie_reply_dev(keys, d, addrs, None, nonces, buf, replies, st)))
+        t_mac1.append(timed(lambda: eng.mac_verify_dev(mac1_keys, 1, d, buf, st1)))
+    assert (st == aead.PKT_COOKIE).all().item() and (st1 == aead.PKT_OK).all().item()
+    ms_c, ms_m = float(np.median(t_cookie)), float(np.median(t_mac1))
+    return {"messages": n, "bytes_each": L, "cookie_reply_ms": round(ms_c, 4),
+            "cookie_reply_mmsg_s": round(n / ms_c / 1e3, 1), "mac1_only_ms": round(ms_m, 4),
+            "mac1_only_mmsg_s": round(n / ms_m / 1e3, 1), "cookie_over_mac1": round(ms_c / ms_m, 2),
+            "note": "medians of 5 alternating repetitions of 20 launches; mac1-only = rg_mac_verify_batch_dev "
+                    "(its key-state launch included) on the same batch; compressions per message 7 vs 2"}
+
+
+def mac1_leg(eng):
     n, L = 1 << 20, 148
     rng = np.random.default_rng(5)
     keys = torch.from_numpy(rng.integers(0, 256, (8, 32), dtype=np.uint8)).cuda()
@@ -52,10 +90,12 @@ def main():
     desc["key_idx"] = aead.KEY_SCAN
     ds = torch.from_numpy(desc.view(np.uint8).reshape(-1, 16)).cuda()
     ms_scan = timed(lambda: eng.mac_verify_dev(keys, 1, ds, buf, st))
-    out["mac1"] = {"messages": n, "bytes_each": L, "own_key_ms": round(ms_own, 4),
-                   "own_key_mmsg_s": round(n / ms_own / 1e3, 1), "scan8_ms": round(ms_scan, 4),
-                   "scan8_mmsg_s": round(n / ms_scan / 1e3, 1)}
-    # ------------------------------------------------------------------ rx
+    return {"messages": n, "bytes_each": L, "own_key_ms": round(ms_own, 4),
+            "own_key_mmsg_s": round(n / ms_own / 1e3, 1), "scan8_ms": round(ms_scan, 4),
+            "scan8_mmsg_s": round(n / ms_scan / 1e3, 1)}
+
+
+def rx_leg(eng):
     w = workloads.build("cfg4")  # 256 sessions: a real table
     b = DeviceBatch(eng, w)
     b.fill()
@@ -77,11 +117,13 @@ def main():
         t_rx.append(timed(lambda: seal_open(True), 10))
     assert (b.status[: w.n] == 0).all().item()
     ms_open, ms_rx = float(np.median(t_open)), float(np.median(t_rx))
-    out["rx"] = {"workload": "cfg4 (1 Mi packets, 256 sessions)", "seal_open_ms": round(ms_open, 4),
-                 "seal_open_rx_ms": round(ms_rx, 4), "resolve_overhead_us": round((ms_rx - ms_open) * 1e3, 2),
-                 "note": "medians of 7 alternating repetitions of 10 steps; the rx_resolve kernel itself is in the "
-                         "rocprofv3 kernel stats"}
-    # ------------------------------------------------------------ sessions
+    return {"workload": "cfg4 (1 Mi packets, 256 sessions)", "seal_open_ms": round(ms_open, 4),
+            "seal_open_rx_ms": round(ms_rx, 4), "resolve_overhead_us": round((ms_rx - ms_open) * 1e3, 2),
+            "note": "medians of 7 alternating repetitions of 10 steps; the rx_resolve kernel itself is in the "
+                    "rocprofv3 kernel stats"}
+
+
+def sessions_leg(eng):
     # the device-resident session layer on config-2 geometry (64 Ki x 1504 B, one session): B seals
     # with rg_send_batch_dev (fresh counters every round), A receives with rg_recv_batch_dev; the host
     # half (rg_recv_batch_dev_finish: in-order anti-replay pass, flags, status write-back) is timed
@@ -117,12 +159,21 @@ def main():
             t_gpu.append(t2 - t1)
             t_fin.append(t3 - t2)
     med = lambda x: float(np.median(x)) * 1e3  # noqa: E731
-    out["sessions"] = {"workload": "cfg2 geometry, one session", "packets": w.n,
-                       "send_batch_dev_ms": round(med(t_send), 4), "recv_batch_dev_ms": round(med(t_gpu), 4),
-                       "recv_finish_ms": round(med(t_fin), 4),
-                       "recv_mpkt_s": round(w.n / (med(t_gpu) + med(t_fin)) / 1e3, 2),
-                       "note": "wall-clock medians of 10 rounds, each call followed by a device sync; finish is "
-                               "the host's in-order anti-replay pass plus the status write-back"}
+    return {"workload": "cfg2 geometry, one session", "packets": w.n,
+            "send_batch_dev_ms": round(med(t_send), 4), "recv_batch_dev_ms": round(med(t_gpu), 4),
+            "recv_finish_ms": round(med(t_fin), 4),
+            "recv_mpkt_s": round(w.n / (med(t_gpu) + med(t_fin)) / 1e3, 2),
+            "note": "wall-clock medians of 10 rounds, each call followed by a device sync; finish is "
+                    "the host's in-order anti-replay pass plus the status write-back"}
+
+
+def main():
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions"]
+    eng = aead.Engine(0)
+    out = {}
+    for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg)):
+        if name in legs:
+            out[name] = leg(eng)
     print(json.dumps(out))
 
 

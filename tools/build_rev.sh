@@ -13,7 +13,8 @@ sched=()
 grep -q "iterative-ilp" "$src/rustyguard_amd/build.py" && sched=(-mllvm -amdgpu-sched-strategy=iterative-ilp)
 mkdir -p tools/build
 objs=()
-for s in rg_kernels.hip rg_tile.hip rg_pipe.hip rg_flat.hip rg_mac.hip rg_api.cpp; do
+for s in rg_kernels.hip rg_tile.hip rg_pipe.hip rg_flat.hip rg_mac.hip rg_cookie.hip rg_api.cpp; do
+    [[ -f "$src/rustyguard_amd/csrc/$s" ]] || continue # a file that revision does not have yet
     x=()
     [[ $s == *.cpp ]] && x=(-x hip)
     [[ $s == rg_pipe.hip || $s == rg_flat.hip ]] && x+=("${sched[@]}")
