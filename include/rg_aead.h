@@ -471,6 +471,61 @@ int rg_recv_batch_dev(rg_sessions *s, const rg_pkt_desc *desc, size_t n, uint8_t
 int rg_recv_batch_dev_finish(rg_sessions *s, const uint64_t *src, uint8_t *status_out, uint32_t *slots_out,
                              uint8_t *flags_out);
 
+/* ------------------------------ device-resident anti-replay (async) */
+/* The RFC 6479 windows in device memory beside the key table, and a receive that never leaves the stream.
+ * Window state is rg_antireplay as defined above, one row per key-table row, 8-byte aligned, owned by the
+ * caller (hipMemset 0 = rg_antireplay_init).  All pointers are device memory; the calls enqueue on `stream`
+ * and return without waiting, allocate nothing and keep nothing in the context (so they can be captured
+ * into a graph): every scratch array lives in `workspace`, 16-byte aligned, of at least
+ * rg_replay_workspace_size(n, nwin) bytes (0 when n is too large for any workspace; non-decreasing in both
+ * arguments).  A workspace belongs to one call at a time: the next call on the same stream may reuse it.
+ *
+ * rg_replay_batch_dev is the in-order tail of DecryptionKey::decrypt (prim.rs:414-437) for a batch.  Its
+ * result equals, bit for bit (status, undo and every byte of every window), this loop over the host
+ * functions above:
+ *   for i in 0..n, in array order:
+ *     w = win_idx[i]
+ *     if w == RG_KEY_SKIP or w >= nwin or status[i] is neither RG_PKT_OK nor RG_PKT_DECRYPT_ERR:
+ *         status[i] stays; undo[i] = 0                       (RG_PKT_PENDING is never turned into a verdict)
+ *     elif !rg_antireplay_would_accept(&windows[w], counters[i]):
+ *         undo[i] = (status[i] == RG_PKT_OK); status[i] = RG_PKT_REJECTED     (also when the tag was bad)
+ *     elif status[i] == RG_PKT_OK:
+ *         rg_antireplay_mark_seen(&windows[w], counters[i]); undo[i] = 0
+ *     else: undo[i] = 0                                      (stays RG_PKT_DECRYPT_ERR, window untouched)
+ * computed in parallel, also within one window (a segmented prefix maximum over each window's packets, a
+ * (window, counter) table for duplicates inside the batch).  undo may be NULL.
+ *
+ * rg_recv_batch_dev_resident is Sessions::decrypt_packet's transport half with no host step: receiver
+ * resolution (as rg_open_batch_dev_rx), the would_accept pre-check of prim.rs:414-420 against the windows as
+ * they stand before the batch (a frame that fails it reaches the open kernels as RG_KEY_SKIP: RG_PKT_REJECTED,
+ * no AEAD work, frame untouched -- exact, since a counter a window rejects is rejected by every later state
+ * of it), the open, the in-order commit above, and the re-seal of frames the open decrypted and the commit
+ * then rejected (byte for byte back to ciphertext, as rg_recv_batch_dev_finish does) -- all enqueued on
+ * `stream`, nothing waited for.  windows[nkeys] runs parallel to the key table.  status gets the FINAL
+ * verdicts (those rg_recv_batch_ex gives for the same frames and windows); counters_out / key_idx_out (may
+ * be NULL) as rg_open_batch_dev_rx, except that a gated packet still reports its header counter and its
+ * resolved key row.  The workspace begins with the call's n working descriptors (rg_pkt_desc rows: the
+ * caller's descriptors with the key row the open ran under, RG_KEY_SKIP for a frame without a session or one
+ * the gate turned away), which a caller may read behind the call.  The call runs the context's open and seal kernels and so shares its planner buffers
+ * with the other device calls: the one-stream rule above applies (a call on another stream while the
+ * context's last batch is in flight fails with RG_EINVAL, nothing enqueued), and a buffer of the context
+ * that has to grow does so outside a stream capture (run the shape once before capturing it).  The endpoint
+ * and keepalive side effects of decrypt_packet (lib.rs:664-679) stay with the host session table: a caller
+ * that wants them reads status and key_idx_out when it chooses to.
+ *
+ * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer (undo, counters_out and
+ * key_idx_out are optional), n > 2^32 - 1, windows not 8-byte or workspace not 16-byte aligned,
+ * workspace_len smaller than rg_replay_workspace_size reports; for the receive also nkeys == 0 or rx_cap
+ * not a power of two. */
+size_t rg_replay_workspace_size(size_t n, uint32_t nwin);
+int rg_replay_batch_dev(rg_ctx *ctx, rg_antireplay *windows, uint32_t nwin, const uint32_t *win_idx,
+                        const uint64_t *counters, size_t n, uint8_t *status, uint8_t *undo, void *workspace,
+                        size_t workspace_len, void *stream);
+int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys, const rg_rx_entry *rx_table,
+                               uint32_t rx_cap, rg_antireplay *windows, const rg_pkt_desc *desc, size_t n,
+                               uint8_t *buf, size_t buf_len, uint8_t *status, uint64_t *counters_out,
+                               uint32_t *key_idx_out, void *workspace, size_t workspace_len, void *stream);
+
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:
  * 349-352; send_message / recv_message :542-583, :605-681).  A group lets that one thread drive

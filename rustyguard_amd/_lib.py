@@ -95,6 +95,10 @@ SIGNATURES = {
     "rg_numa_bind": (c_int, [c_vp, c_size, c_int]),
     "rg_host_register": (c_int, [c_vp, c_size]),
     "rg_host_unregister": (c_int, [c_vp]),
+    "rg_replay_workspace_size": (c_size, [c_size, c_u32]),
+    "rg_replay_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_recv_batch_dev_resident": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_size, c_vp,
+                                           c_vp, c_vp, c_vp, c_size, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

@@ -221,6 +221,50 @@ class Engine:
                                                       _vp(status), _stream_handle(stream)),
                     "rg_cookie_reply_batch_dev")
 
+    def replay_workspace(self, n: int, nwin: int, device=None):
+        """The scratch tensor (uint8, on this engine's device) that replay_batch_dev / recv_batch_dev_resident
+        need for a batch of n packets over nwin windows (rg_replay_workspace_size)."""
+        import torch
+
+        size = int(self._L.rg_replay_workspace_size(n, nwin))
+        if size == 0:
+            raise _lib.RgError(f"no workspace can hold a batch of {n} packets")
+        return torch.empty(size, dtype=torch.uint8, device=device if device is not None else f"cuda:{self.device}")
+
+    def replay_batch_dev(self, windows, win_idx, counters, status, undo=None, workspace=None, stream=None):
+        """rg_replay_batch_dev: the in-order anti-replay commit of a batch on the device.  windows: rg_antireplay
+        rows (264 bytes each), win_idx uint32 / counters uint64 / status uint8 one per packet (status updated in
+        place), undo (uint8, optional) = 1 where an RG_PKT_OK packet was rejected.  Returns the workspace used."""
+        n = _nbytes(status)
+        nwin = _nbytes(windows) // 264
+        assert _nbytes(windows) % 264 == 0 and _nbytes(win_idx) >= 4 * n and _nbytes(counters) >= 8 * n
+        assert undo is None or _nbytes(undo) >= n
+        if workspace is None:
+            workspace = self.replay_workspace(n, nwin)
+        self._check(self._L.rg_replay_batch_dev(self._h, _vp(windows), nwin, _vp(win_idx), _vp(counters), n, _vp(status),
+                                                _vp(undo), _vp(workspace), _nbytes(workspace), _stream_handle(stream)),
+                    "rg_replay_batch_dev")
+        return workspace
+
+    def recv_batch_dev_resident(self, keys, rx_table, windows, desc, buf, status, counters_out=None, key_idx_out=None,
+                                workspace=None, stream=None):
+        """rg_recv_batch_dev_resident: receiver resolution, would_accept gate, open, in-order commit and re-seal
+        of rejected frames, all on `stream` with no host step.  windows: one rg_antireplay row (264 bytes) per
+        key row.  status gets the final verdicts.  Returns the workspace used (its first 16 n bytes are the
+        working descriptors the open ran under)."""
+        n = _ndesc(desc)
+        nkeys = _nbytes(keys) // 32
+        cap = _nbytes(rx_table) // 8
+        assert _nbytes(windows) >= 264 * nkeys and _nbytes(status) >= n
+        if workspace is None:
+            workspace = self.replay_workspace(n, nkeys)
+        self._check(self._L.rg_recv_batch_dev_resident(self._h, _vp(keys), nkeys, _vp(rx_table), cap, _vp(windows),
+                                                       _vp(desc), n, _vp(buf), _nbytes(buf), _vp(status),
+                                                       _vp(counters_out), _vp(key_idx_out), _vp(workspace),
+                                                       _nbytes(workspace), _stream_handle(stream)),
+                    "rg_recv_batch_dev_resident")
+        return workspace
+
     def synth_fill_dev(self, desc, inner_len, buf, seed: int, stream=None):
         n = _ndesc(desc)
         self._check(self._L.rg_synth_fill_dev(self._h, _vp(desc), _vp(inner_len), n, _vp(buf), _nbytes(buf), seed,

@@ -23,7 +23,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librg_aead.so")
 TEST_LIB = os.path.join(LIBDIR, "librg_aead_test.so")
-KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip"]
+KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip",
+           "rg_replay.hip"]
 API = "rg_api.cpp"
 SOURCES = KERNELS + [API]
 HEADERS = ["rg_device.h", "rg_internal.h", "rg_blake2s.h"]

@@ -532,6 +532,7 @@ void mark_stream(rg_ctx *ctx, hipStream_t st, hipEvent_t ev) {
 // rg_internal.h: the context as seen by entry points outside this file (rg_cookie.hip)
 int rg::ctx_select(rg_ctx *ctx) { return check_ctx(ctx); }
 int rg::api_error(int code, const char *what, hipError_t e) { return set_err(code, what, e); }
+int rg::ctx_claim_stream(rg_ctx *ctx, hipStream_t st) { return claim_stream(ctx, st); }
 
 extern "C" {
 

@@ -60,6 +60,63 @@ hipError_t launch_mac_verify(const MacArgs &a, hipStream_t s);
 int ctx_select(rg_ctx *ctx);
 // records the text rg_last_error() returns on this thread (with HIP's error string when e is one); returns code
 int api_error(int code, const char *what, hipError_t e = hipSuccess);
+// the one-stream rule of the device API (include/rg_aead.h) for an entry point that enqueues kernels of its
+// own ahead of rg_open_batch_dev / rg_seal_batch_dev: RG_OK, or RG_EINVAL (recorded) while the context's
+// last batch is still in flight on another stream.  An event query, no wait.
+int ctx_claim_stream(rg_ctx *ctx, hipStream_t st);
+
+// Workspace of the device anti-replay calls (rg_replay.hip): byte offsets of its arrays from the caller's
+// 16-byte aligned base, each a multiple of 256.  total == 0: the batch is too large.
+constexpr uint32_t kReplayTile = 2048; // packets per workgroup of the scan and radix passes
+struct ReplayLayout {
+    uint64_t rdesc; // [n] rg_pkt_desc: working descriptors of the open (RG_KEY_SKIP = unknown or gated); = 0
+    // commit pass
+    uint64_t hash;     // [hash_cap] u32: earliest RG_PKT_OK packet of each (window, counter)
+    uint64_t order[2]; // [n] u32 each: packet indices grouped by window (ping-pong of the radix passes)
+    uint64_t hist;     // [256][nblk] u32: digit counts per workgroup
+    uint64_t agg_val;  // [nblk] u64 and
+    uint64_t agg_flag; // [nblk] u32: per-workgroup aggregates of the segmented prefix maximum
+    uint64_t lf;       // [n] u64: the running maximum at each window's last packet
+    // resident receive (rdesc at offset 0: include/rg_aead.h documents it to callers)
+    uint64_t ctr;     // [n] u64: header counters
+    uint64_t widx;    // [n] u32: resolved key rows = window rows
+    uint64_t undo;    // [n] u8
+    uint64_t ustatus; // [n] u8: statuses of the re-seal
+    uint64_t udesc;   // [n] rg_pkt_desc: re-seal descriptors
+    uint64_t total;
+    uint64_t hash_cap; // a power of two >= 2 n
+    uint32_t nblk;     // workgroups of kReplayTile packets
+    uint32_t passes;   // 8-bit radix passes over the window index (0: one window, no grouping)
+};
+inline ReplayLayout replay_layout(uint64_t n, uint32_t nwin) {
+    ReplayLayout L{};
+    if (n > 0xFFFFFFFFull) return L; // total = 0
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    };
+    L.hash_cap = 64;
+    while (L.hash_cap < 2 * n) L.hash_cap <<= 1;
+    L.nblk = (uint32_t)((n + kReplayTile - 1) / kReplayTile);
+    for (uint32_t top = nwin ? nwin - 1 : 0; top; top >>= 8) ++L.passes;
+    L.rdesc = take(n * sizeof(rg_pkt_desc));
+    L.hash = take(L.hash_cap * 4);
+    L.order[0] = take(L.passes > 0 ? n * 4 : 0);
+    L.order[1] = take(L.passes > 1 ? n * 4 : 0);
+    L.hist = take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
+    L.agg_val = take((uint64_t)L.nblk * 8);
+    L.agg_flag = take((uint64_t)L.nblk * 4);
+    L.lf = take(n * 8);
+    L.ctr = take(n * 8);
+    L.widx = take(n * 4);
+    L.undo = take(n);
+    L.ustatus = take(n);
+    L.udesc = take(n * sizeof(rg_pkt_desc));
+    L.total = at ? at : 256;
+    return L;
+}
 
 // The caller's current HIP device, put back on the way out: every entry point selects its context's
 // device (and a group call each of its contexts' in turn), while the caller -- a torch program, say --

@@ -1,0 +1,579 @@
+// rg_replay.hip -- the RFC 6479 anti-replay window on the device, batched: the in-order tail of
+// DecryptionKey::decrypt (rustyguard-crypto/src/prim.rs:414-437; AntiReplay::{would_accept, mark_seen},
+// rustyguard-utils/src/anti_replay.rs:25-64) for a whole batch, and a receive that never leaves the stream
+// (rg_recv_batch_dev_resident: resolve + gate, open, commit, re-seal of what the commit rejected).
+//
+// The sequential rule has a closed form over a batch ("Device-resident anti-replay").  For
+// window w with last = L0 at the start and S = its packets, in array order, whose status is OK or
+// DECRYPT_ERR:
+//   M_p    = max(L0, counters of the OK packets of S before p)         a segmented prefix maximum
+//   p is REJECTED iff  ctr_p <= M_p and M_p - ctr_p >= 1984            too old
+//                  or  ctr_p <= M_p, ctr_p's block <= L0's block and its bit is set in the window as it
+//                      stood at the start                              seen before the batch
+//                  or  an earlier OK packet of S has the same counter  seen in the batch
+//   last'  = M over all of S; slot j & 31 of the bitmap, for the block j in (last' / 64 - 32, last' / 64],
+//            keeps its starting word when j <= L0 / 64 and starts from zero otherwise, OR the bits of the
+//            accepted packets of block j.
+//
+// Kernels of the commit pass, all on the call's stream:
+//   radix_hist / radix_scan / radix_scatter   stable grouping of the packet indices by window: an LSD radix
+//            sort over the window index, 8 bits per pass, as many passes as the window count needs (none
+//            for one window: the array is its own grouping)
+//   replay_clear    the (window, counter) table starts empty
+//   replay_reduce   per workgroup of 2048 grouped packets the aggregate of the segmented prefix maximum;
+//            every OK packet enters the (window, counter) table, the smallest packet index winning
+//   replay_carry    one workgroup scans the aggregates
+//   replay_verdict  every packet's M_p, the three tests, status and undo; the running maximum at each
+//            window's last packet
+//   replay_advance  one lane per window with traffic: the slots the window moved past are cleared, last'
+//   replay_mark     the accepted packets' bits (64-bit atomic OR)
+// A packet without a window (RG_KEY_SKIP, out of range) or without a verdict to judge (any status but OK /
+// DECRYPT_ERR, RG_PKT_PENDING included) rides along in window 0's group as a neutral element and comes
+// back untouched.
+//
+// The entry points' host side is here too (rg_cookie.hip's precedent): rg_api.cpp names no launcher of
+// this file.  All scratch is the caller's workspace; nothing is allocated, waited for or kept.
+#include "rg_device.h"
+#include "rg_internal.h"
+
+namespace rg {
+namespace {
+
+constexpr uint32_t kItems = kReplayTile / 256; // grouped packets per lane, consecutive
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;       // (window, counter) table: free slot (n <= 2^32 - 1)
+
+struct ReplayArgs {
+    rg_antireplay *windows;
+    const uint32_t *win_idx;  // [n]
+    const uint64_t *counters; // [n]
+    uint8_t *status;          // [n]
+    uint8_t *undo;            // [n] or nullptr
+    const uint32_t *order;    // [n] packet indices grouped by window, or nullptr: array order
+    uint32_t *hash;
+    uint64_t hash_mask;
+    uint64_t *agg_val;
+    uint32_t *agg_flag;
+    uint64_t *lf;
+    uint32_t nwin;
+    uint32_t n;
+    uint32_t nblk;
+};
+
+// (the grouped order is a permutation of [0, n); the bound keeps every later access inside the batch's
+// arrays whatever the workspace holds)
+__device__ __forceinline__ uint32_t index_at(const ReplayArgs &a, uint64_t pos) {
+    return a.order ? min(a.order[pos], a.n - 1) : (uint32_t)pos;
+}
+__device__ __forceinline__ bool has_window(const ReplayArgs &a, uint32_t w) { return w != RG_KEY_SKIP && w < a.nwin; }
+// the grouping key: a packet's window, 0 for a packet without one
+__device__ __forceinline__ uint32_t group_of(const ReplayArgs &a, uint32_t i) {
+    const uint32_t w = a.win_idx[i];
+    return has_window(a, w) ? w : 0u;
+}
+
+// ------------------------------------------------------- grouping by window
+// One pass of a stable LSD radix sort: workgroup b owns positions [b, b + 1) x kReplayTile of src.
+__global__ __launch_bounds__(256) void radix_hist_kernel(ReplayArgs a, const uint32_t *src, uint32_t shift,
+                                                         uint32_t *hist) {
+    __shared__ uint32_t s_h[256];
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile;
+    for (uint32_t k = 0; k < kItems; ++k) {
+        const uint64_t pos = base + k * 256 + threadIdx.x;
+        if (pos < a.n) atomicAdd(&s_h[(group_of(a, src ? src[pos] : (uint32_t)pos) >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * a.nblk + blockIdx.x] = s_h[threadIdx.x];
+}
+
+// exclusive prefix sum over hist[0, total), digit-major: one workgroup, a contiguous run per lane
+__global__ __launch_bounds__(1024) void radix_scan_kernel(uint32_t *hist, uint64_t total) {
+    __shared__ uint32_t s_sum[1024];
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = (total + 1023) / 1024, lo = min(t * per, total), hi = min(lo + per, total);
+    uint32_t sum = 0;
+    for (uint64_t j = lo; j < hi; ++j) sum += hist[j];
+    s_sum[t] = sum;
+    __syncthreads();
+    uint32_t cur = sum;
+    for (uint32_t off = 1; off < 1024; off <<= 1) {
+        const uint32_t o = t >= off ? s_sum[t - off] : 0u;
+        __syncthreads();
+        cur += o;
+        s_sum[t] = cur;
+        __syncthreads();
+    }
+    uint32_t run = cur - sum;
+    for (uint64_t j = lo; j < hi; ++j) {
+        const uint32_t c = hist[j];
+        hist[j] = run;
+        run += c;
+    }
+}
+
+// Stable scatter: wave v of the workgroup owns the contiguous quarter v of the tile and walks it 64
+// positions at a time; lanes of one round with the same digit find each other by ballots and take
+// consecutive places behind the digit's running offset.
+__global__ __launch_bounds__(256) void radix_scatter_kernel(ReplayArgs a, const uint32_t *src, uint32_t *dst,
+                                                            uint32_t shift, const uint32_t *hist) {
+    __shared__ uint32_t s_off[4][256];
+    const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
+    for (uint32_t q = 0; q < 4; ++q) s_off[q][t] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + v * (kReplayTile / 4);
+    constexpr uint32_t kRounds = kReplayTile / 256;
+    uint32_t idx[kRounds], dg[kRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint64_t pos = base + r * 64 + lane;
+        const bool ok = pos < a.n;
+        idx[r] = ok ? (src ? src[pos] : (uint32_t)pos) : 0u;
+        dg[r] = ok ? (group_of(a, idx[r]) >> shift) & 255u : 256u;
+        if (ok) atomicAdd(&s_off[v][dg[r]], 1u);
+    }
+    __syncthreads();
+    { // counts -> first place of (wave, digit): the workgroup's base, then the waves in order
+        uint32_t run = hist[(uint64_t)t * a.nblk + blockIdx.x];
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint32_t c = s_off[q][t];
+            s_off[q][t] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const bool ok = dg[r] < 256u;
+        uint64_t same = __ballot(ok);
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            const bool bit = (dg[r] >> b) & 1u;
+            const uint64_t m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1));
+        const uint32_t off = ok ? s_off[v][dg[r]] : 0u;
+        __syncthreads();
+        if (ok && rank == 0) s_off[v][dg[r]] = off + (uint32_t)__popcll(same);
+        if (ok) dst[(uint64_t)off + rank] = idx[r];
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------- segmented prefix maximum
+// (f, v): f = the run holds a window's first packet, v = the largest OK counter since the last such
+// packet (0 when none: every window's last is >= 0).  join is associative.
+struct Pair {
+    uint32_t f;
+    uint64_t v;
+};
+__device__ __forceinline__ Pair join(const Pair &a, const Pair &b) {
+    return Pair{a.f | b.f, b.f ? b.v : (a.v > b.v ? a.v : b.v)};
+}
+
+// exclusive prefix of one Pair per lane over the workgroup's 256 lanes (returned), and their total
+__device__ __forceinline__ Pair block_prefix(const Pair &mine, Pair &total) {
+    __shared__ uint32_t s_f[256];
+    __shared__ uint64_t s_v[256];
+    const uint32_t t = threadIdx.x;
+    s_f[t] = mine.f;
+    s_v[t] = mine.v;
+    __syncthreads();
+    Pair cur = mine;
+    for (uint32_t off = 1; off < 256; off <<= 1) {
+        const bool has = t >= off;
+        Pair o{0u, 0ull};
+        if (has) o = Pair{s_f[t - off], s_v[t - off]};
+        __syncthreads();
+        if (has) {
+            cur = join(o, cur);
+            s_f[t] = cur.f;
+            s_v[t] = cur.v;
+        }
+        __syncthreads();
+    }
+    total = Pair{s_f[255], s_v[255]};
+    return t ? Pair{s_f[t - 1], s_v[t - 1]} : Pair{0u, 0ull};
+}
+
+// ------------------------------------------- (window, counter) -> earliest OK packet
+__device__ __forceinline__ uint64_t hash_slot(uint32_t w, uint64_t c, uint64_t mask) {
+    uint64_t x = c ^ ((uint64_t)w * 0x9E3779B97F4A7C15ull);
+    x ^= x >> 32;
+    x *= 0xD6E8FEB86659FD93ull;
+    x ^= x >> 32;
+    x *= 0xD6E8FEB86659FD93ull;
+    x ^= x >> 32;
+    return x & mask;
+}
+
+// A slot holds the index of a packet with the slot's key; packets of one key lower it to their smallest
+// index.  Once taken, a slot's key never changes, so a probe compares against whichever index it reads.
+// The table has at least two slots per packet: a probe ends.
+__device__ __forceinline__ void hash_insert(const ReplayArgs &a, uint32_t i, uint32_t w, uint64_t c) {
+    for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
+        const uint32_t e = atomicCAS(&a.hash[s], kEmpty, i);
+        if (e == kEmpty) return;
+        if (a.win_idx[e] == w && a.counters[e] == c) {
+            atomicMin(&a.hash[s], i);
+            return;
+        }
+    }
+}
+__device__ __forceinline__ uint32_t hash_find(const ReplayArgs &a, uint32_t w, uint64_t c) {
+    for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
+        const uint32_t e = a.hash[s];
+        if (e == kEmpty) return kEmpty;
+        if (a.win_idx[e] == w && a.counters[e] == c) return e;
+    }
+}
+
+__global__ __launch_bounds__(256) void replay_clear_kernel(uint4 *hash4, uint64_t quads) {
+    for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (uint64_t)gridDim.x * 256)
+        hash4[q] = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
+}
+
+// one grouped packet as the scan sees it
+struct Item {
+    uint32_t i, w, key;
+    uint32_t st; // status, or 0xFF beyond the batch
+    uint64_t ctr;
+    bool head;
+};
+__device__ __forceinline__ Item load_item(const ReplayArgs &a, uint64_t pos, uint32_t prev_key) {
+    Item it{};
+    it.i = index_at(a, pos);
+    it.w = a.win_idx[it.i];
+    const bool win = has_window(a, it.w);
+    it.key = win ? it.w : 0u;
+    it.st = win ? a.status[it.i] : 0xFFu;
+    it.ctr = win && it.st <= RG_PKT_DECRYPT_ERR ? a.counters[it.i] : 0ull;
+    it.head = pos == 0 || it.key != prev_key;
+    return it;
+}
+__device__ __forceinline__ Pair pair_of(const Item &it) {
+    return Pair{it.head ? 1u : 0u, it.st == RG_PKT_OK ? it.ctr : 0ull};
+}
+
+__global__ __launch_bounds__(256) void replay_reduce_kernel(ReplayArgs a) {
+    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + threadIdx.x * kItems;
+    uint32_t prev = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    Pair run{0u, 0ull};
+    for (uint32_t k = 0; k < kItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos >= a.n) break;
+        const Item it = load_item(a, pos, prev);
+        prev = it.key;
+        if (it.st == RG_PKT_OK) hash_insert(a, it.i, it.w, it.ctr);
+        run = join(run, pair_of(it));
+    }
+    Pair total;
+    (void)block_prefix(run, total);
+    if (threadIdx.x == 0) {
+        a.agg_flag[blockIdx.x] = total.f;
+        a.agg_val[blockIdx.x] = total.v;
+    }
+}
+
+// aggregates -> what each workgroup starts from (exclusive), in place; one workgroup
+__global__ __launch_bounds__(256) void replay_carry_kernel(ReplayArgs a) {
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (a.nblk + 255) / 256, lo = min(t * per, a.nblk), hi = min(lo + per, a.nblk);
+    Pair run{0u, 0ull};
+    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{a.agg_flag[j], a.agg_val[j]});
+    Pair total;
+    Pair ex = block_prefix(run, total);
+    for (uint32_t j = lo; j < hi; ++j) {
+        const Pair cur{a.agg_flag[j], a.agg_val[j]};
+        a.agg_flag[j] = ex.f;
+        a.agg_val[j] = ex.v;
+        ex = join(ex, cur);
+    }
+}
+
+__global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
+    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + threadIdx.x * kItems;
+    uint32_t prev = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    Item items[kItems];
+    Pair run{0u, 0ull};
+#pragma unroll
+    for (uint32_t k = 0; k < kItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos < a.n) {
+            items[k] = load_item(a, pos, prev);
+            prev = items[k].key;
+            run = join(run, pair_of(items[k]));
+        } else {
+            items[k] = Item{};
+            items[k].st = 0xFFu;
+        }
+    }
+    Pair total;
+    const Pair mine = block_prefix(run, total);
+    Pair ex = join(Pair{a.agg_flag[blockIdx.x], a.agg_val[blockIdx.x]}, mine);
+#pragma unroll
+    for (uint32_t k = 0; k < kItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos >= a.n) break;
+        const Item &it = items[k];
+        const uint64_t before = it.head ? 0ull : ex.v; // largest OK counter of the window ahead of this packet
+        ex = join(ex, pair_of(it));
+        uint8_t undo = 0;
+        if (it.st <= RG_PKT_DECRYPT_ERR) { // has a window and a verdict to judge
+            const rg_antireplay &win = a.windows[it.w];
+            const uint64_t L0 = win.last, M = before > L0 ? before : L0, c = it.ctr;
+            bool rej = false;
+            if (c <= M) {
+                if (M - c >= RG_REPLAY_WINDOW) rej = true;
+                else if ((c >> 6) <= (L0 >> 6) && ((win.bitmap[(c >> 6) & 31] >> (c & 63)) & 1ull)) rej = true;
+                else {
+                    const uint32_t first = hash_find(a, it.w, c);
+                    rej = first != kEmpty && first < it.i;
+                }
+            }
+            if (rej) {
+                undo = it.st == RG_PKT_OK;
+                a.status[it.i] = RG_PKT_REJECTED; // also for a bad tag: would_accept comes first
+            }
+        }
+        if (a.undo) a.undo[it.i] = undo;
+        // the window's last packet of the batch hands the running maximum to replay_advance
+        const bool tail = pos + 1 == a.n || group_of(a, index_at(a, pos + 1)) != it.key;
+        if (tail) a.lf[pos] = ex.v;
+    }
+}
+
+// One lane per window with traffic (the lane of its last grouped packet): the slots of the blocks the
+// window moved past start from zero, then last.  Both branches of mark_seen: a jump of more than 32
+// blocks leaves no block j <= L0 / 64 in reach, so every slot is cleared.
+__global__ __launch_bounds__(256) void replay_advance_kernel(ReplayArgs a) {
+    const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pos >= a.n) return;
+    const uint32_t key = group_of(a, index_at(a, pos));
+    if (pos + 1 != a.n && group_of(a, index_at(a, pos + 1)) == key) return;
+    if (key >= a.nwin) return; // no window at all
+    rg_antireplay &win = a.windows[key];
+    const uint64_t L0 = win.last, Lf = a.lf[pos];
+    if (Lf <= L0) return; // nothing accepted above last: no slot changes hands
+    const uint64_t bf = Lf >> 6, b0 = L0 >> 6;
+    for (uint32_t s = 0; s < 32; ++s) {
+        const uint64_t back = (bf - s) & 31u; // slot s holds block bf - back
+        if (back <= bf && bf - back > b0) win.bitmap[s] = 0;
+    }
+    win.last = Lf;
+}
+
+__global__ __launch_bounds__(256) void replay_mark_kernel(ReplayArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const uint32_t w = a.win_idx[i];
+    if (!has_window(a, w) || a.status[i] != RG_PKT_OK) return;
+    rg_antireplay &win = a.windows[w];
+    const uint64_t c = a.counters[i];
+    if ((win.last >> 6) - (c >> 6) < 32) // else the window has moved past its block since
+        atomicOr(reinterpret_cast<unsigned long long *>(&win.bitmap[(c >> 6) & 31]), 1ull << (c & 63));
+}
+
+// packets without windows at all (nwin == 0): nothing to judge
+__global__ __launch_bounds__(256) void replay_none_kernel(uint8_t *undo, uint32_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) undo[i] = 0;
+}
+
+hipError_t launch_commit(rg_antireplay *windows, uint32_t nwin, const uint32_t *win_idx, const uint64_t *counters,
+                         uint32_t n, uint8_t *status, uint8_t *undo, uint8_t *ws, const ReplayLayout &L,
+                         hipStream_t st) {
+    const dim3 per_packet((n + 255) / 256), wg(256);
+    if (nwin == 0) {
+        if (undo) hipLaunchKernelGGL(replay_none_kernel, per_packet, wg, 0, st, undo, n);
+        return hipGetLastError();
+    }
+    ReplayArgs a{};
+    a.windows = windows;
+    a.win_idx = win_idx;
+    a.counters = counters;
+    a.status = status;
+    a.undo = undo;
+    a.hash = reinterpret_cast<uint32_t *>(ws + L.hash);
+    a.hash_mask = L.hash_cap - 1;
+    a.agg_val = reinterpret_cast<uint64_t *>(ws + L.agg_val);
+    a.agg_flag = reinterpret_cast<uint32_t *>(ws + L.agg_flag);
+    a.lf = reinterpret_cast<uint64_t *>(ws + L.lf);
+    a.nwin = nwin;
+    a.n = n;
+    a.nblk = L.nblk;
+    const dim3 tiles(L.nblk);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.hist);
+    const uint32_t *src = nullptr;
+    for (uint32_t p = 0; p < L.passes; ++p) {
+        uint32_t *dst = reinterpret_cast<uint32_t *>(ws + L.order[p & 1]);
+        hipLaunchKernelGGL(radix_hist_kernel, tiles, wg, 0, st, a, src, 8 * p, hist);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, st, hist, 256ull * L.nblk);
+        hipLaunchKernelGGL(radix_scatter_kernel, tiles, wg, 0, st, a, src, dst, 8 * p, (const uint32_t *)hist);
+        src = dst;
+    }
+    a.order = src;
+    const uint64_t quads = L.hash_cap / 4;
+    hipLaunchKernelGGL(replay_clear_kernel, dim3((uint32_t)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048)), wg, 0, st,
+                       reinterpret_cast<uint4 *>(a.hash), quads);
+    hipLaunchKernelGGL(replay_reduce_kernel, tiles, wg, 0, st, a);
+    hipLaunchKernelGGL(replay_carry_kernel, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(replay_verdict_kernel, tiles, wg, 0, st, a);
+    hipLaunchKernelGGL(replay_advance_kernel, per_packet, wg, 0, st, a);
+    hipLaunchKernelGGL(replay_mark_kernel, per_packet, wg, 0, st, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------- resident receive
+struct ResidentArgs {
+    const rg_pkt_desc *desc;
+    const uint8_t *buf;
+    uint64_t buf_len;
+    const rg_rx_entry *table;
+    uint32_t cap;
+    const rg_antireplay *windows;
+    uint32_t nkeys;
+    uint32_t n;
+    rg_pkt_desc *rdesc;
+    uint64_t *ctr;
+    uint32_t *widx;
+    uint32_t *key_out;      // or nullptr
+    const uint8_t *undo;    // undo pass
+    rg_pkt_desc *udesc;     // undo pass
+    uint64_t *counters_out; // undo pass, or nullptr
+};
+
+// rx_resolve_kernel (rg_kernels.hip) with the would_accept pre-check of prim.rs:414-420: a frame whose
+// session is known and whose header counter the window, as it stands before the batch, would not accept
+// goes to the open kernels as RG_KEY_SKIP -- RG_PKT_REJECTED, no AEAD work, frame untouched.  Exact: last
+// only grows, and a seen bit leaves the window only when its counter has become too old.
+__global__ __launch_bounds__(256) void resident_gate_kernel(ResidentArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    rg_pkt_desc d = a.desc[i];
+    const uint64_t W = d.len;
+    uint32_t k = 0, found = RG_KEY_SKIP;
+    uint64_t ctr = 0;
+    if ((d.offset & 15u) == 0 && d.offset <= a.buf_len && W <= a.buf_len - d.offset && W >= 16 && (W & 15u) == 0) {
+        const uint4 hdr = *reinterpret_cast<const uint4 *>(a.buf + d.offset);
+        if (hdr.x == 4u) {
+            ctr = ((uint64_t)hdr.w << 32) | hdr.z;
+            uint32_t s = rx_slot(hdr.y, a.cap);
+            for (uint32_t probe = 0; probe < a.cap; ++probe) {
+                const rg_rx_entry e = a.table[s];
+                if (e.key_idx == RG_KEY_SKIP) break;
+                if (e.receiver == hdr.y) {
+                    found = e.key_idx;
+                    break;
+                }
+                s = (s + 1) & (a.cap - 1);
+            }
+            k = found;
+            if (found != RG_KEY_SKIP && found < a.nkeys) {
+                const rg_antireplay &win = a.windows[found];
+                const uint64_t last = win.last;
+                if (ctr <= last &&
+                    (last - ctr >= RG_REPLAY_WINDOW || ((win.bitmap[(ctr >> 6) & 31] >> (ctr & 63)) & 1ull)))
+                    k = RG_KEY_SKIP;
+            }
+        }
+    }
+    d.key_idx = k;
+    a.rdesc[i] = d;
+    a.ctr[i] = ctr;
+    a.widx[i] = found;
+    if (a.key_out) a.key_out[i] = found;
+}
+
+// Re-seal descriptors of the frames the open decrypted and the commit then rejected (payload W - 32, the
+// open's key row; RG_KEY_SKIP for every other packet), and the header counter of a gated packet, which
+// the open kernels did not report.
+__global__ __launch_bounds__(256) void resident_undo_kernel(ResidentArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const rg_pkt_desc d = a.rdesc[i];
+    rg_pkt_desc u{0, 0, RG_KEY_SKIP};
+    if (a.undo[i]) u = rg_pkt_desc{d.offset, d.len - 32, d.key_idx};
+    a.udesc[i] = u;
+    if (a.counters_out && d.key_idx == RG_KEY_SKIP && a.widx[i] != RG_KEY_SKIP) a.counters_out[i] = a.ctr[i];
+}
+
+} // namespace
+} // namespace rg
+
+extern "C" size_t rg_replay_workspace_size(size_t n, uint32_t nwin) { return (size_t)rg::replay_layout(n, nwin).total; }
+
+extern "C" int rg_replay_batch_dev(rg_ctx *ctx, rg_antireplay *windows, uint32_t nwin, const uint32_t *win_idx,
+                                   const uint64_t *counters, size_t n, uint8_t *status, uint8_t *undo,
+                                   void *workspace, size_t workspace_len, void *stream) {
+    rg::DeviceGuard dg_;
+    const int rc = rg::ctx_select(ctx);
+    if (rc) return rc;
+    if (n == 0) return RG_OK;
+    if (!windows || !win_idx || !counters || !status || !workspace || n > 0xFFFFFFFFull)
+        return rg::api_error(RG_EINVAL, "replay: bad args");
+    if (((uintptr_t)windows & 7u) || ((uintptr_t)workspace & 15u))
+        return rg::api_error(RG_EINVAL, "replay: windows must be 8-byte and workspace 16-byte aligned");
+    const rg::ReplayLayout L = rg::replay_layout(n, nwin);
+    if (L.total == 0 || workspace_len < L.total)
+        return rg::api_error(RG_EINVAL, "replay: workspace smaller than rg_replay_workspace_size");
+    const hipError_t e = rg::launch_commit(windows, nwin, win_idx, counters, (uint32_t)n, status, undo,
+                                           static_cast<uint8_t *>(workspace), L, (hipStream_t)stream);
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "replay launch", e);
+    return RG_OK;
+}
+
+extern "C" int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys,
+                                          const rg_rx_entry *rx_table, uint32_t rx_cap, rg_antireplay *windows,
+                                          const rg_pkt_desc *desc, size_t n, uint8_t *buf, size_t buf_len,
+                                          uint8_t *status, uint64_t *counters_out, uint32_t *key_idx_out,
+                                          void *workspace, size_t workspace_len, void *stream) {
+    rg::DeviceGuard dg_;
+    int rc = rg::ctx_select(ctx);
+    if (rc) return rc;
+    if (n == 0) return RG_OK;
+    if (!keys || nkeys == 0 || !rx_table || rx_cap == 0 || (rx_cap & (rx_cap - 1)) != 0 || !windows || !desc || !buf ||
+        !status || !workspace || n > 0xFFFFFFFFull)
+        return rg::api_error(RG_EINVAL, "recv resident: bad args");
+    if (((uintptr_t)windows & 7u) || ((uintptr_t)workspace & 15u))
+        return rg::api_error(RG_EINVAL, "recv resident: windows must be 8-byte and workspace 16-byte aligned");
+    const rg::ReplayLayout L = rg::replay_layout(n, nkeys);
+    if (L.total == 0 || workspace_len < L.total)
+        return rg::api_error(RG_EINVAL, "recv resident: workspace smaller than rg_replay_workspace_size");
+    hipStream_t st = (hipStream_t)stream;
+    rc = rg::ctx_claim_stream(ctx, st); // before anything is enqueued
+    if (rc) return rc;
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    rg::ResidentArgs a{};
+    a.desc = desc;
+    a.buf = buf;
+    a.buf_len = buf_len;
+    a.table = rx_table;
+    a.cap = rx_cap;
+    a.windows = windows;
+    a.nkeys = nkeys;
+    a.n = (uint32_t)n;
+    a.rdesc = reinterpret_cast<rg_pkt_desc *>(ws + L.rdesc);
+    a.ctr = reinterpret_cast<uint64_t *>(ws + L.ctr);
+    a.widx = reinterpret_cast<uint32_t *>(ws + L.widx);
+    a.key_out = key_idx_out;
+    uint8_t *undo = ws + L.undo;
+    a.undo = undo;
+    a.udesc = reinterpret_cast<rg_pkt_desc *>(ws + L.udesc);
+    a.counters_out = counters_out;
+    const dim3 grid((uint32_t)((n + 255) / 256)), wg(256);
+    hipLaunchKernelGGL(rg::resident_gate_kernel, grid, wg, 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: gate launch", e);
+    rc = rg_open_batch_dev(ctx, keys, nkeys, a.rdesc, n, buf, buf_len, status, counters_out, stream);
+    if (rc) return rc;
+    e = rg::launch_commit(windows, nkeys, a.widx, a.ctr, (uint32_t)n, status, undo, ws, L, st);
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: commit launch", e);
+    hipLaunchKernelGGL(rg::resident_undo_kernel, grid, wg, 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: undo launch", e);
+    // re-seal under the same key row and counter: ciphertext and tag come back byte for byte; without
+    // receivers the header is not rewritten (rg_recv_batch_dev_finish)
+    return rg_seal_batch_dev(ctx, keys, nullptr, nkeys, a.udesc, a.ctr, n, buf, buf_len, ws + L.ustatus, stream);
+}

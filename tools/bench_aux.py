@@ -9,6 +9,12 @@
   rx     rg_open_batch_dev_rx vs rg_open_batch_dev on config 4 frames (256 sessions): the cost of
          resolving every frame's session from its header on the device
 
+  replay the device-frame receive on cfg2 (64 Ki x 1500 B, one session) and cfg4 (256 sessions x 4 Ki x 1500 B),
+         same frames, three ways in one run: (a) rg_open_batch_dev_rx alone (the floor), (b) rg_recv_batch_dev +
+         rg_recv_batch_dev_finish (host wall clock: the path waits on the host), (c) rg_recv_batch_dev_resident;
+         fresh counters only, and 10 % replays of the previous batch.  Also written to
+         profiles/replay_resident_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -167,11 +173,114 @@ def sessions_leg(eng):
                     "the host's in-order anti-replay pass plus the status write-back"}
 
 
+def replay_leg(eng):
+    import ctypes
+    import time
+
+    def shape(cfg):
+        w = workloads.build(cfg)
+        n, nk = w.n, len(w.receivers)
+        b = DeviceBatch(eng, w)
+        off = w.desc["offset"].astype(np.int64)
+        stride = int(off[1] - off[0])
+        assert (np.diff(off) == stride).all() and w.buf_bytes >= n * stride
+        rows = lambda t: t[: n * stride].view(n, stride)  # noqa: E731
+        # batch 1 (the workload's counters) and batch 2 (the same sessions, 2^24 further on)
+        b.fill()
+        b.seal()
+        batch1 = b.buf.clone()
+        b.fill()
+        eng.seal_dev(b.keys, b.receivers, b.desc_seal, b.counters + (1 << 24), b.buf, b.status)
+        fresh = b.buf.clone()
+        mixed = fresh.clone()
+        rows(mixed)[::10] = rows(batch1)[::10]  # 10 % replays of the previous batch
+        torch.cuda.synchronize()
+        table = torch.from_numpy(aead.rx_table(w.receivers, np.arange(nk, dtype=np.uint32))).cuda()
+        ws = eng.replay_workspace(n, nk)
+        win = torch.zeros(nk * 33, dtype=torch.int64, device="cuda")
+        eng.recv_batch_dev_resident(b.keys, table, win, b.desc_open, batch1.clone(), b.status, workspace=ws)
+        torch.cuda.synchronize()
+        assert (b.status[:n] == 0).all().item()
+        win1 = win.clone()  # the windows after batch 1
+        tab = aead.Sessions(eng, nk)
+        slots = [tab.insert(int(w.receivers[s]), 0x70000000 + s, bytes(32), w.keys.reshape(-1, 32)[s].tobytes())
+                 for s in range(nk)]
+        host1 = win1.cpu().numpy().view(np.uint8).reshape(nk, 264)
+        ptrs = [eng.library.rg_sessions_replay(tab._h, sl) for sl in slots]
+
+        def restore(frames):
+            b.buf.copy_(frames)
+            win.copy_(win1)
+            for s, p in enumerate(ptrs):
+                ctypes.memmove(p, host1[s].ctypes.data, 264)
+            torch.cuda.synchronize()
+
+        def gpu_ms(fn):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            z.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(z)
+
+        def wall_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def floor():
+            eng.open_dev_rx(b.keys, table, b.desc_open, b.buf, b.status)
+
+        def parent():
+            tab.recv_batch_dev(b.desc_open, b.buf, b.status)
+            tab.recv_batch_dev_finish(n)
+
+        def resident():
+            eng.recv_batch_dev_resident(b.keys, table, win, b.desc_open, b.buf, b.status, workspace=ws)
+
+        out = {"packets": n, "sessions": nk}
+        for mix, frames in (("fresh", fresh), ("replay10", mixed)):
+            t = {"a_open_rx_gpu_ms": [], "b_parent_wall_ms": [], "c_resident_gpu_ms": [], "c_resident_wall_ms": []}
+            want = None
+            for rep in range(9):
+                restore(frames)
+                t["a_open_rx_gpu_ms"].append(gpu_ms(floor))
+                restore(frames)
+                t["b_parent_wall_ms"].append(wall_ms(parent))
+                st_b = b.status[:n].clone()
+                restore(frames)
+                t["c_resident_gpu_ms"].append(gpu_ms(resident))
+                assert torch.equal(b.status[:n], st_b), "resident and parent paths disagree"
+                restore(frames)
+                t["c_resident_wall_ms"].append(wall_ms(resident))
+                want = int((st_b == 3).sum().item())
+            r = {k: {"median": round(float(np.median(v[2:])), 4), "min": round(min(v[2:]), 4),
+                     "max": round(max(v[2:]), 4)} for k, v in t.items()}
+            r["rejected"] = want
+            r["c_over_a"] = round(r["c_resident_gpu_ms"]["median"] / r["a_open_rx_gpu_ms"]["median"], 3)
+            r["b_over_c"] = round(r["b_parent_wall_ms"]["median"] / r["c_resident_wall_ms"]["median"], 3)
+            out[mix] = r
+        return out
+
+    res = {"cfg2": shape("cfg2"), "cfg4": shape("cfg4"),
+           "note": "9 alternating repetitions per mix, the first two dropped; frames, device windows and the session "
+                   "table's windows restored outside the timed region; (a) and (c) by stream events, (b) and (c) "
+                   "also by host wall clock around the calls and a device sync"}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                        "replay_resident_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay"]
     eng = aead.Engine(0)
     out = {}
-    for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg)):
+    for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
+                      ("replay", replay_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
