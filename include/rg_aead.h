@@ -526,6 +526,69 @@ int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys,
                                uint8_t *buf, size_t buf_len, uint8_t *status, uint64_t *counters_out,
                                uint32_t *key_idx_out, void *workspace, size_t workspace_len, void *stream);
 
+/* ------------------------------------ device-resident send (async) */
+/* The send counters in device memory beside the key table, and a send that never leaves the stream: the
+ * transmit half of the section above, with the same conventions.  One rg_send_state row per key-table row,
+ * 8-byte aligned, owned by the caller (a new session: counter = 0, started_ns = sent_ns = its start time).
+ * All pointers are device memory; the calls enqueue on `stream` and return without waiting, allocate nothing
+ * and keep nothing in the context (so they can be captured into a graph): every scratch array lives in
+ * `workspace`, 16-byte aligned, of at least rg_send_workspace_size(n, nkeys) bytes (0 when n is too large for
+ * any workspace; non-decreasing in both arguments).  A workspace belongs to one call at a time: the next
+ * call on the same stream may reuse it.  slots[i] is packet i's key-table row; desc[i].key_idx is ignored.
+ * now_ns points to one u64 in device memory, read when the kernels run (a captured graph sees each replay's
+ * clock); NULL: no time rule, and sent_ns is left untouched.
+ *
+ * rg_send_reserve_batch_dev is the counter pass alone: the sequential part of EncryptionKey::encrypt
+ * (prim.rs:386-394) and PeerState::force_encrypt (lib.rs:260-297) for a batch.  Its result equals, bit for
+ * bit (status, counters_out, rekey_out and every byte of every state row), rg_send_batch's loop over the
+ * device state:
+ *   for i in 0..n, in array order:
+ *     w = slots[i]; rekey_out[i] = 0; counters_out[i] = 0
+ *     if w == RG_KEY_SKIP or w >= nkeys:                         status[i] = RG_PKT_REJECTED
+ *     elif desc[i].len % 16 != 0:                                status[i] = RG_PKT_INVALID   (takes no counter)
+ *     elif state[w].counter >= RG_REJECT_AFTER_MESSAGES
+ *       or (now_ns and state[w].started_ns + 180e9 < *now_ns):   status[i] = RG_PKT_REJECTED  (u64 wrapping add)
+ *     else: counters_out[i] = state[w].counter++; if now_ns: state[w].sent_ns = *now_ns
+ *           rekey_out[i] = state[w].counter >= RG_REKEY_AFTER_MESSAGES
+ *           status[i] = RG_PKT_PENDING       (a counter is reserved; only a seal lane may write RG_PKT_OK)
+ * computed in parallel, also within one row, and never by atomics in arrival order: a stable grouping of the
+ * packets by row and a segmented count of the eligible ones give each packet its rank.  rekey_out
+ * may be NULL.  The workspace begins with the call's n working descriptors (rg_pkt_desc rows: the caller's
+ * descriptors with key_idx = w, RG_KEY_SKIP for every packet that took no counter), which a caller may read
+ * behind the call or hand to rg_seal_batch_dev with counters_out.
+ *
+ * rg_send_batch_dev_resident is that pass followed by rg_seal_batch_dev over the working descriptors and the
+ * reserved counters (header from receivers[w], encrypted in place, tag written), all enqueued on `stream`,
+ * nothing waited for.  state[nkeys] runs parallel to the key table.  status gets the FINAL verdicts: the
+ * pass's RG_PKT_REJECTED / RG_PKT_INVALID (frame untouched), otherwise what the seal kernel wrote -- also
+ * RG_PKT_UNALIGNED / RG_PKT_INVALID for a misaligned or out-of-bounds frame, which has consumed its counter
+ * exactly as in rg_send_batch (nonces stay unique).  counters_out and rekey_out may be NULL.  The call runs
+ * the context's seal kernels and so shares its planner buffers with the other device calls: the one-stream
+ * rule above applies (a call on another stream while the context's last batch is in flight fails with
+ * RG_EINVAL, nothing enqueued), and a buffer of the context that has to grow does so outside a stream
+ * capture (run the shape once before capturing it).  The keepalive timer stays with the caller, which reads
+ * sent_ns when it chooses to.
+ *
+ * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer (now_ns and rekey_out are
+ * optional, for the resident call also counters_out), n > 2^32 - 1, state not 8-byte or workspace not 16-byte
+ * aligned, workspace_len smaller than rg_send_workspace_size reports; for the resident call also nkeys == 0. */
+typedef struct rg_send_state {
+    uint64_t counter;    /* EncryptionKey.counter: the next counter to hand out */
+    uint64_t started_ns; /* Session.started (REJECT_AFTER_TIME, lib.rs:204-209) */
+    uint64_t sent_ns;    /* Session.sent (force_encrypt, lib.rs:285; read by the keepalive rule) */
+} rg_send_state;         /* 24 bytes */
+
+size_t rg_send_workspace_size(size_t n, uint32_t nkeys);
+int rg_send_reserve_batch_dev(rg_ctx *ctx, rg_send_state *state, uint32_t nkeys, const uint32_t *slots,
+                              const rg_pkt_desc *desc, size_t n, const uint64_t *now_ns, uint8_t *status,
+                              uint64_t *counters_out, uint8_t *rekey_out, void *workspace, size_t workspace_len,
+                              void *stream);
+int rg_send_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, const uint32_t *receivers, uint32_t nkeys,
+                               rg_send_state *state, const uint32_t *slots, const rg_pkt_desc *desc, size_t n,
+                               const uint64_t *now_ns, uint8_t *buf, size_t buf_len, uint8_t *status,
+                               uint64_t *counters_out, uint8_t *rekey_out, void *workspace, size_t workspace_len,
+                               void *stream);
+
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:
  * 349-352; send_message / recv_message :542-583, :605-681).  A group lets that one thread drive

@@ -99,6 +99,11 @@ SIGNATURES = {
     "rg_replay_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_size, c_vp]),
     "rg_recv_batch_dev_resident": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_size, c_vp,
                                            c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_send_workspace_size": (c_size, [c_size, c_u32]),
+    "rg_send_reserve_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_size,
+                                          c_vp]),
+    "rg_send_batch_dev_resident": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_size, c_vp,
+                                           c_vp, c_vp, c_vp, c_size, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

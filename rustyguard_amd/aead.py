@@ -265,6 +265,55 @@ class Engine:
                     "rg_recv_batch_dev_resident")
         return workspace
 
+    def send_workspace(self, n: int, nkeys: int, device=None):
+        """The scratch tensor (uint8, on this engine's device) that send_reserve_batch_dev / send_batch_dev_resident
+        need for a batch of n packets over nkeys rows (rg_send_workspace_size)."""
+        import torch
+
+        size = int(self._L.rg_send_workspace_size(n, nkeys))
+        if size == 0:
+            raise _lib.RgError(f"no workspace can hold a batch of {n} packets")
+        return torch.empty(size, dtype=torch.uint8, device=device if device is not None else f"cuda:{self.device}")
+
+    def send_reserve_batch_dev(self, state, slots, desc, status, counters_out, rekey_out=None, now_ns=None,
+                               workspace=None, stream=None):
+        """rg_send_reserve_batch_dev: the send counters of a batch handed out on the device, in array order.
+        state: rg_send_state rows (24 bytes each: counter, started_ns, sent_ns), slots uint32 / status uint8 /
+        counters_out uint64 one per packet, rekey_out (uint8, optional), now_ns a device tensor holding one
+        uint64 (None: no time rule).  Returns the workspace used (its first 16 n bytes are the working
+        descriptors for a seal under counters_out)."""
+        n = _ndesc(desc)
+        nkeys = _nbytes(state) // 24
+        assert _nbytes(state) % 24 == 0 and _nbytes(slots) >= 4 * n and _nbytes(status) >= n
+        assert _nbytes(counters_out) >= 8 * n and (rekey_out is None or _nbytes(rekey_out) >= n)
+        assert now_ns is None or _nbytes(now_ns) >= 8
+        if workspace is None:
+            workspace = self.send_workspace(n, nkeys)
+        self._check(self._L.rg_send_reserve_batch_dev(self._h, _vp(state), nkeys, _vp(slots), _vp(desc), n, _vp(now_ns),
+                                                      _vp(status), _vp(counters_out), _vp(rekey_out), _vp(workspace),
+                                                      _nbytes(workspace), _stream_handle(stream)),
+                    "rg_send_reserve_batch_dev")
+        return workspace
+
+    def send_batch_dev_resident(self, keys, receivers, state, slots, desc, buf, status, counters_out=None,
+                                rekey_out=None, now_ns=None, workspace=None, stream=None):
+        """rg_send_batch_dev_resident: counters reserved on the device, then the seal, all on `stream` with no
+        host step.  state: one rg_send_state row (24 bytes) per key row.  status gets the final verdicts.
+        Returns the workspace used."""
+        n = _ndesc(desc)
+        nkeys = _nbytes(keys) // 32
+        assert _nbytes(state) >= 24 * nkeys and _nbytes(receivers) >= 4 * nkeys and _nbytes(slots) >= 4 * n
+        assert _nbytes(status) >= n and (counters_out is None or _nbytes(counters_out) >= 8 * n)
+        assert (rekey_out is None or _nbytes(rekey_out) >= n) and (now_ns is None or _nbytes(now_ns) >= 8)
+        if workspace is None:
+            workspace = self.send_workspace(n, nkeys)
+        self._check(self._L.rg_send_batch_dev_resident(self._h, _vp(keys), _vp(receivers), nkeys, _vp(state), _vp(slots),
+                                                       _vp(desc), n, _vp(now_ns), _vp(buf), _nbytes(buf), _vp(status),
+                                                       _vp(counters_out), _vp(rekey_out), _vp(workspace),
+                                                       _nbytes(workspace), _stream_handle(stream)),
+                    "rg_send_batch_dev_resident")
+        return workspace
+
     def synth_fill_dev(self, desc, inner_len, buf, seed: int, stream=None):
         n = _ndesc(desc)
         self._check(self._L.rg_synth_fill_dev(self._h, _vp(desc), _vp(inner_len), n, _vp(buf), _nbytes(buf), seed,

@@ -24,10 +24,10 @@ LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "librg_aead.so")
 TEST_LIB = os.path.join(LIBDIR, "librg_aead_test.so")
 KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip",
-           "rg_replay.hip"]
+           "rg_replay.hip", "rg_send.hip"]
 API = "rg_api.cpp"
 SOURCES = KERNELS + [API]
-HEADERS = ["rg_device.h", "rg_internal.h", "rg_blake2s.h"]
+HEADERS = ["rg_device.h", "rg_internal.h", "rg_blake2s.h", "rg_radix.h"]
 ARCH = os.environ.get("RG_OFFLOAD_ARCH", "gfx950")
 # Per-file code generation.  The pipelined and flattened kernels run one wave per SIMD, so nothing hides a
 # hazard wait state: LLVM's iterative-ILP machine scheduler fills most of the s_nops the default strategy

@@ -1124,11 +1124,40 @@ hipError_t launch_flat(const SealArgs *sa, const OpenArgs *oa, bool balance, uin
                        hipEvent_t done) {
     const uint32_t n = sa ? sa->n : oa->n;
     if (n == 0) return hipSuccess;
+    // one workgroup per CU (two, at two waves per SIMD, measured 5-8 % slower: profiles/r4_cfg3_twowave_ab.txt)
+    const uint32_t blocks = (uint32_t)(cus > 0 ? cus : 1);
+    // A unit belongs to the group of kFlatGroup packets its nominal start u n / units falls in.  A short last
+    // group lies behind the last unit's start when (units - 1) n / units is below its first packet (2049
+    // packets on 1024 units: packet 2048), and no wave would take it: it runs as a launch of its own
+    // behind the whole groups, which then divide the units among themselves.
+    const uint64_t units = (uint64_t)blocks * kFlatWaves, head = (uint64_t)(n - 1) / kFlatGroup * kFlatGroup;
+    if (head > 0 && n <= kFlatGroup * units && (units - 1) * n < head * units) {
+        SealArgs s2[2];
+        OpenArgs o2[2];
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t at = k ? (uint32_t)head : 0u, m = k ? n - (uint32_t)head : (uint32_t)head;
+            if (sa) {
+                s2[k] = *sa;
+                s2[k].desc += at;
+                s2[k].counters += at;
+                if (s2[k].status) s2[k].status += at;
+                s2[k].n = m;
+            } else {
+                o2[k] = *oa;
+                o2[k].desc += at;
+                o2[k].status += at;
+                if (o2[k].counters_out) o2[k].counters_out += at;
+                o2[k].n = m;
+            }
+            const hipError_t e = launch_flat(sa ? &s2[k] : nullptr, oa ? &o2[k] : nullptr, balance, junk, cus, s,
+                                             k ? done : nullptr);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
     FlatArgs A{};
     if (sa) A.sa = *sa;
     if (oa) A.oa = *oa;
-    // one workgroup per CU (two, at two waves per SIMD, measured 5-8 % slower: profiles/r4_cfg3_twowave_ab.txt)
-    const uint32_t blocks = (uint32_t)(cus > 0 ? cus : 1);
     A.units = blocks * kFlatWaves;
     A.junk = junk;
     A.balance = balance ? 1u : 0u;

@@ -16,7 +16,7 @@
 //            accepted packets of block j.
 //
 // Kernels of the commit pass, all on the call's stream:
-//   radix_hist / radix_scan / radix_scatter   stable grouping of the packet indices by window: an LSD radix
+//   radix_hist / radix_scan / radix_scatter   (rg_radix.h) stable grouping of the packet indices by window: an LSD radix
 //            sort over the window index, 8 bits per pass, as many passes as the window count needs (none
 //            for one window: the array is its own grouping)
 //   replay_clear    the (window, counter) table starts empty
@@ -35,6 +35,7 @@
 // this file.  All scratch is the caller's workspace; nothing is allocated, waited for or kept.
 #include "rg_device.h"
 #include "rg_internal.h"
+#include "rg_radix.h"
 
 namespace rg {
 namespace {
@@ -72,94 +73,15 @@ __device__ __forceinline__ uint32_t group_of(const ReplayArgs &a, uint32_t i) {
 }
 
 // ------------------------------------------------------- grouping by window
-// One pass of a stable LSD radix sort: workgroup b owns positions [b, b + 1) x kReplayTile of src.
-__global__ __launch_bounds__(256) void radix_hist_kernel(ReplayArgs a, const uint32_t *src, uint32_t shift,
-                                                         uint32_t *hist) {
-    __shared__ uint32_t s_h[256];
-    s_h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile;
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k * 256 + threadIdx.x;
-        if (pos < a.n) atomicAdd(&s_h[(group_of(a, src ? src[pos] : (uint32_t)pos) >> shift) & 255u], 1u);
+// the key of the shared radix passes (rg_radix.h)
+struct WindowKey {
+    const uint32_t *win_idx;
+    uint32_t nwin;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
+        const uint32_t w = win_idx[i];
+        return w != RG_KEY_SKIP && w < nwin ? w : 0u;
     }
-    __syncthreads();
-    hist[(uint64_t)threadIdx.x * a.nblk + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// exclusive prefix sum over hist[0, total), digit-major: one workgroup, a contiguous run per lane
-__global__ __launch_bounds__(1024) void radix_scan_kernel(uint32_t *hist, uint64_t total) {
-    __shared__ uint32_t s_sum[1024];
-    const uint32_t t = threadIdx.x;
-    const uint64_t per = (total + 1023) / 1024, lo = min(t * per, total), hi = min(lo + per, total);
-    uint32_t sum = 0;
-    for (uint64_t j = lo; j < hi; ++j) sum += hist[j];
-    s_sum[t] = sum;
-    __syncthreads();
-    uint32_t cur = sum;
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        const uint32_t o = t >= off ? s_sum[t - off] : 0u;
-        __syncthreads();
-        cur += o;
-        s_sum[t] = cur;
-        __syncthreads();
-    }
-    uint32_t run = cur - sum;
-    for (uint64_t j = lo; j < hi; ++j) {
-        const uint32_t c = hist[j];
-        hist[j] = run;
-        run += c;
-    }
-}
-
-// Stable scatter: wave v of the workgroup owns the contiguous quarter v of the tile and walks it 64
-// positions at a time; lanes of one round with the same digit find each other by ballots and take
-// consecutive places behind the digit's running offset.
-__global__ __launch_bounds__(256) void radix_scatter_kernel(ReplayArgs a, const uint32_t *src, uint32_t *dst,
-                                                            uint32_t shift, const uint32_t *hist) {
-    __shared__ uint32_t s_off[4][256];
-    const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
-    for (uint32_t q = 0; q < 4; ++q) s_off[q][t] = 0;
-    __syncthreads();
-    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + v * (kReplayTile / 4);
-    constexpr uint32_t kRounds = kReplayTile / 256;
-    uint32_t idx[kRounds], dg[kRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const uint64_t pos = base + r * 64 + lane;
-        const bool ok = pos < a.n;
-        idx[r] = ok ? (src ? src[pos] : (uint32_t)pos) : 0u;
-        dg[r] = ok ? (group_of(a, idx[r]) >> shift) & 255u : 256u;
-        if (ok) atomicAdd(&s_off[v][dg[r]], 1u);
-    }
-    __syncthreads();
-    { // counts -> first place of (wave, digit): the workgroup's base, then the waves in order
-        uint32_t run = hist[(uint64_t)t * a.nblk + blockIdx.x];
-        for (uint32_t q = 0; q < 4; ++q) {
-            const uint32_t c = s_off[q][t];
-            s_off[q][t] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
-        const bool ok = dg[r] < 256u;
-        uint64_t same = __ballot(ok);
-#pragma unroll
-        for (uint32_t b = 0; b < 8; ++b) {
-            const bool bit = (dg[r] >> b) & 1u;
-            const uint64_t m = __ballot(bit);
-            same &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1));
-        const uint32_t off = ok ? s_off[v][dg[r]] : 0u;
-        __syncthreads();
-        if (ok && rank == 0) s_off[v][dg[r]] = off + (uint32_t)__popcll(same);
-        if (ok) dst[(uint64_t)off + rank] = idx[r];
-        __syncthreads();
-    }
-}
+};
 
 // ------------------------------------------- segmented prefix maximum
 // (f, v): f = the run holds a window's first packet, v = the largest OK counter since the last such
@@ -404,16 +326,8 @@ hipError_t launch_commit(rg_antireplay *windows, uint32_t nwin, const uint32_t *
     a.n = n;
     a.nblk = L.nblk;
     const dim3 tiles(L.nblk);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.hist);
-    const uint32_t *src = nullptr;
-    for (uint32_t p = 0; p < L.passes; ++p) {
-        uint32_t *dst = reinterpret_cast<uint32_t *>(ws + L.order[p & 1]);
-        hipLaunchKernelGGL(radix_hist_kernel, tiles, wg, 0, st, a, src, 8 * p, hist);
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, st, hist, 256ull * L.nblk);
-        hipLaunchKernelGGL(radix_scatter_kernel, tiles, wg, 0, st, a, src, dst, 8 * p, (const uint32_t *)hist);
-        src = dst;
-    }
-    a.order = src;
+    a.order = group_by_key(WindowKey{win_idx, nwin}, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
+                           reinterpret_cast<uint32_t *>(ws + L.order[0]), reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
     const uint64_t quads = L.hash_cap / 4;
     hipLaunchKernelGGL(replay_clear_kernel, dim3((uint32_t)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048)), wg, 0, st,
                        reinterpret_cast<uint4 *>(a.hash), quads);

@@ -1,0 +1,406 @@
+// rg_send.hip -- send counters reserved on the device, batched: the sequential part of
+// EncryptionKey::encrypt (rustyguard-crypto/src/prim.rs:376-399: `counter` handed out and incremented) and
+// PeerState::force_encrypt (rustyguard-core/src/lib.rs:260-297: should_reject / should_expire, `sent`) for a
+// whole batch, and a send that never leaves the stream (rg_send_batch_dev_resident: reserve, seal, verdicts).
+//
+// The array-order loop (include/rg_aead.h, rg_send_reserve_batch_dev) has a closed form over a batch
+// ("Device-resident send").  For row w with counter = C0 at the start and E = its eligible
+// packets in array order (valid row, len % 16 == 0, row not expired -- none of which the loop changes):
+//   packet of rank r in E takes C0 + r   iff  C0 < REJECT and r < REJECT - C0      (ranks are compared, never
+//                                             C0 + r with REJECT: that sum can wrap 64 bits)
+//   rekey = C0 + r + 1 >= REKEY
+//   counter' = C0 + min(|E|, REJECT - C0) (unchanged for C0 >= REJECT), sent' = now iff a packet took one
+// r is a stable segmented exclusive count of eligibility flags over the packets grouped by row.
+//
+// Kernels, all on the call's stream:
+//   radix_hist / radix_scan / radix_scatter   (rg_radix.h) stable grouping of the packet indices by row; none
+//            for one row: the array is its own grouping
+//   send_reduce    per workgroup of 2048 grouped packets the aggregate of the segmented count: each wave
+//            walks its quarter 64 packets a round (ballots of eligibility and of row heads, popcounts), the
+//            four waves meet in LDS
+//   send_carry     one workgroup scans the aggregates
+//   send_verdict   every packet's rank, then status, counter, rekey flag and working descriptor; |E| at each
+//            row's last packet
+//   send_update    one lane per row with traffic: counter', sent'
+//   send_overlay   (resident send) the verdicts of packets without a counter over the seal's statuses
+// A packet without a row (RG_KEY_SKIP, out of range) rides along in row 0's group, not eligible.
+// Plain vector stores only; no atomics on global memory.
+//
+// The entry points' host side is here too (rg_replay.hip's precedent).  All scratch is the caller's
+// workspace; nothing is allocated, waited for or kept.
+#include "rg_device.h"
+#include "rg_internal.h"
+#include "rg_radix.h"
+
+namespace rg {
+namespace {
+
+constexpr uint64_t kRejectAfterTimeNs = 180ull * 1000000000ull; // REJECT_AFTER_TIME, lib.rs:204-209
+constexpr uint32_t kRounds = kRadixTile / 256;                  // rounds of 64 packets per wave
+
+// Workspace of the device send calls: byte offsets from the caller's 16-byte aligned base, each a multiple
+// of 256.  total == 0: the batch is too large.  Every term is non-decreasing in n and in nkeys.
+struct SendLayout {
+    uint64_t wdesc;    // [n] rg_pkt_desc: working descriptors (RG_KEY_SKIP = took no counter); = 0
+    uint64_t order[2]; // [n] u32 each: packet indices grouped by row (ping-pong of the radix passes)
+    uint64_t hist;     // [256][nblk] u32
+    uint64_t agg_val;  // [nblk] u32 and
+    uint64_t agg_flag; // [nblk] u32: per-workgroup aggregates of the segmented count
+    uint64_t tot;      // [n] u32: |E| at each row's last grouped packet
+    uint64_t verdict;  // [n] u8: the reserve's statuses (resident send)
+    uint64_t ctr;      // [n] u64: reserved counters when the caller passes no counters_out (resident send)
+    uint64_t total;
+    uint32_t nblk;
+    uint32_t passes;
+};
+SendLayout send_layout(uint64_t n, uint32_t nkeys) {
+    SendLayout L{};
+    if (n > 0xFFFFFFFFull) return L;
+    uint64_t at = 0;
+    auto take = [&at](uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    };
+    L.nblk = (uint32_t)((n + kRadixTile - 1) / kRadixTile);
+    L.passes = radix_passes(nkeys);
+    L.wdesc = take(n * sizeof(rg_pkt_desc));
+    L.order[0] = take(L.passes > 0 ? n * 4 : 0);
+    L.order[1] = take(L.passes > 1 ? n * 4 : 0);
+    L.hist = take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
+    L.agg_val = take((uint64_t)L.nblk * 4);
+    L.agg_flag = take((uint64_t)L.nblk * 4);
+    L.tot = take(n * 4);
+    L.verdict = take(n);
+    L.ctr = take(n * 8);
+    L.total = at ? at : 256;
+    return L;
+}
+
+struct SendArgs {
+    rg_send_state *state;
+    const uint32_t *slots;   // [n]
+    const rg_pkt_desc *desc; // [n]
+    const uint64_t *now_ns;  // one u64, or nullptr: no time rule
+    uint8_t *status;         // [n]
+    uint64_t *counters_out;  // [n]
+    uint8_t *rekey_out;      // [n] or nullptr
+    rg_pkt_desc *wdesc;      // [n]
+    const uint32_t *order;   // [n] packet indices grouped by row, or nullptr: array order
+    uint32_t *agg_val;
+    uint32_t *agg_flag;
+    uint32_t *tot;
+    uint32_t nkeys;
+    uint32_t n;
+    uint32_t nblk;
+};
+
+struct RowKey { // the key of the shared radix passes: a packet's row, 0 for a packet without one
+    const uint32_t *slots;
+    uint32_t nkeys;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
+        const uint32_t w = slots[i];
+        return w != RG_KEY_SKIP && w < nkeys ? w : 0u;
+    }
+};
+
+// (the grouped order is a permutation of [0, n); the bound keeps every later access inside the batch's
+// arrays whatever the workspace holds)
+__device__ __forceinline__ uint32_t index_at(const SendArgs &a, uint64_t pos) {
+    return a.order ? min(a.order[pos], a.n - 1) : (uint32_t)pos;
+}
+__device__ __forceinline__ bool has_row(const SendArgs &a, uint32_t w) { return w != RG_KEY_SKIP && w < a.nkeys; }
+__device__ __forceinline__ uint32_t group_of(const SendArgs &a, uint32_t i) {
+    const uint32_t w = a.slots[i];
+    return has_row(a, w) ? w : 0u;
+}
+__device__ __forceinline__ bool expired(const SendArgs &a, uint32_t w, bool timed, uint64_t now) {
+    return timed && a.state[w].started_ns + kRejectAfterTimeNs < now; // u64 wrapping add, as the host
+}
+
+// (f, v): f = the run holds a row's first packet, v = eligible packets since the last such packet.
+struct Pair {
+    uint32_t f, v;
+};
+__device__ __forceinline__ Pair join(const Pair &a, const Pair &b) { return Pair{a.f | b.f, b.f ? b.v : a.v + b.v}; }
+
+// One grouped packet as the scan sees it.  (f, v) is the packet's exclusive prefix inside its wave's quarter
+// of the tile: f = a row began at or before it there, v = eligible packets of its row ahead of it there.
+struct Item {
+    uint32_t i, w; // packet index, its slot word; i == 0xFFFFFFFF beyond the batch
+    uint32_t key;
+    uint32_t f, v;
+    bool elig;
+};
+
+// The workgroup's tile: wave v owns the contiguous quarter v and walks it 64 positions a round.  Fills
+// items[] and returns the exclusive prefix of this wave inside the tile; `total` is the tile's aggregate.
+__device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kRounds], Pair &total) {
+    __shared__ uint32_t s_f[4], s_v[4];
+    const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
+    const uint64_t base = (uint64_t)blockIdx.x * kRadixTile + v * (kRadixTile / 4);
+    const bool timed = a.now_ns != nullptr;
+    const uint64_t now = timed ? *a.now_ns : 0ull;
+    const uint64_t below = (1ull << lane) - 1, upto = (2ull << lane) - 1;
+    // the key ahead of this wave's first position (a row's head is a change of key)
+    uint32_t last_key = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    Pair run{0u, 0u};
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint64_t pos = base + r * 64 + lane;
+        Item it{0xFFFFFFFFu, RG_KEY_SKIP, 0u, 0u, 0u, false};
+        bool head = false;
+        if (pos < a.n) {
+            it.i = index_at(a, pos);
+            it.w = a.slots[it.i];
+            const bool row = has_row(a, it.w);
+            it.key = row ? it.w : 0u;
+            it.elig = row && (a.desc[it.i].len & 15u) == 0 && !expired(a, it.w, timed, now);
+        }
+        const uint32_t up = __shfl_up(it.key, 1);
+        const uint32_t prev = lane ? up : last_key;
+        if (pos < a.n) head = pos == 0 || it.key != prev;
+        const uint64_t H = __ballot(head), E = __ballot(it.elig);
+        const uint64_t hm = H & upto;
+        if (hm) { // the packet's row began in this round
+            const uint32_t s = 63u - (uint32_t)__clzll((long long)hm);
+            it.f = 1u;
+            it.v = (uint32_t)__popcll(E & below & ~((1ull << s) - 1));
+        } else {
+            it.f = run.f;
+            it.v = run.v + (uint32_t)__popcll(E & below);
+        }
+        items[r] = it;
+        if (H) {
+            const uint32_t s = 63u - (uint32_t)__clzll((long long)H);
+            run = Pair{1u, (uint32_t)__popcll(E & ~((1ull << s) - 1))};
+        } else {
+            run.v += (uint32_t)__popcll(E);
+        }
+        last_key = __shfl(it.key, 63);
+    }
+    if (lane == 0) {
+        s_f[v] = run.f;
+        s_v[v] = run.v;
+    }
+    __syncthreads();
+    Pair ex{0u, 0u}, all{0u, 0u};
+    for (uint32_t q = 0; q < 4; ++q) {
+        if (q == v) ex = all;
+        all = join(all, Pair{s_f[q], s_v[q]});
+    }
+    total = all;
+    return ex;
+}
+
+__global__ __launch_bounds__(256) void send_reduce_kernel(SendArgs a) {
+    Item items[kRounds];
+    Pair total;
+    (void)tile_scan(a, items, total);
+    if (threadIdx.x == 0) {
+        a.agg_flag[blockIdx.x] = total.f;
+        a.agg_val[blockIdx.x] = total.v;
+    }
+}
+
+// aggregates -> what each workgroup starts from (exclusive), in place; one workgroup
+__global__ __launch_bounds__(256) void send_carry_kernel(SendArgs a) {
+    __shared__ uint32_t s_f[256], s_v[256];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (a.nblk + 255) / 256, lo = min(t * per, a.nblk), hi = min(lo + per, a.nblk);
+    Pair run{0u, 0u};
+    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{a.agg_flag[j], a.agg_val[j]});
+    s_f[t] = run.f;
+    s_v[t] = run.v;
+    __syncthreads();
+    Pair cur = run;
+    for (uint32_t off = 1; off < 256; off <<= 1) {
+        const bool has = t >= off;
+        Pair o{0u, 0u};
+        if (has) o = Pair{s_f[t - off], s_v[t - off]};
+        __syncthreads();
+        if (has) {
+            cur = join(o, cur);
+            s_f[t] = cur.f;
+            s_v[t] = cur.v;
+        }
+        __syncthreads();
+    }
+    Pair ex = t ? Pair{s_f[t - 1], s_v[t - 1]} : Pair{0u, 0u};
+    for (uint32_t j = lo; j < hi; ++j) {
+        const Pair c{a.agg_flag[j], a.agg_val[j]};
+        a.agg_flag[j] = ex.f;
+        a.agg_val[j] = ex.v;
+        ex = join(ex, c);
+    }
+}
+
+__global__ __launch_bounds__(256) void send_verdict_kernel(SendArgs a) {
+    Item items[kRounds];
+    Pair total;
+    const Pair wave_ex = tile_scan(a, items, total);
+    const Pair ex = join(Pair{a.agg_flag[blockIdx.x], a.agg_val[blockIdx.x]}, wave_ex);
+    const uint32_t v = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint64_t base = (uint64_t)blockIdx.x * kRadixTile + v * (kRadixTile / 4);
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const Item &it = items[r];
+        const uint64_t pos = base + r * 64 + lane;
+        if (pos >= a.n) continue;
+        const uint64_t rank = it.f ? (uint64_t)it.v : (uint64_t)ex.v + it.v; // eligible packets of the row ahead
+        rg_pkt_desc d = a.desc[it.i];
+        d.key_idx = RG_KEY_SKIP;
+        uint64_t ctr = 0;
+        uint8_t st = RG_PKT_REJECTED, rekey = 0;
+        if (has_row(a, it.w)) {
+            if ((d.len & 15u) != 0) st = RG_PKT_INVALID; // takes no counter
+            else if (it.elig) {                          // else the row has expired
+                const uint64_t C0 = a.state[it.w].counter;
+                const uint64_t room = C0 < RG_REJECT_AFTER_MESSAGES ? RG_REJECT_AFTER_MESSAGES - C0 : 0ull;
+                if (rank < room) {
+                    ctr = C0 + rank; // < REJECT: neither this sum nor ctr + 1 wraps
+                    rekey = ctr + 1 >= RG_REKEY_AFTER_MESSAGES;
+                    st = RG_PKT_PENDING; // a counter is reserved; only a seal lane may write RG_PKT_OK
+                    d.key_idx = it.w;
+                }
+            }
+        }
+        a.status[it.i] = st;
+        a.counters_out[it.i] = ctr;
+        if (a.rekey_out) a.rekey_out[it.i] = rekey;
+        a.wdesc[it.i] = d;
+        // the row's last packet of the batch hands |E| to send_update
+        const bool tail = pos + 1 == a.n || group_of(a, index_at(a, pos + 1)) != it.key;
+        if (tail) a.tot[pos] = (uint32_t)rank + (it.elig ? 1u : 0u);
+    }
+}
+
+// One lane per row with traffic (the lane of its last grouped packet).
+__global__ __launch_bounds__(256) void send_update_kernel(SendArgs a) {
+    const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pos >= a.n) return;
+    const uint32_t key = group_of(a, index_at(a, pos));
+    if (pos + 1 != a.n && group_of(a, index_at(a, pos + 1)) == key) return;
+    if (key >= a.nkeys) return;
+    rg_send_state &row = a.state[key];
+    const uint64_t C0 = row.counter, E = a.tot[pos];
+    const uint64_t room = C0 < RG_REJECT_AFTER_MESSAGES ? RG_REJECT_AFTER_MESSAGES - C0 : 0ull;
+    const uint64_t took = E < room ? E : room;
+    if (took == 0) return; // the row stays byte for byte
+    row.counter = C0 + took;
+    if (a.now_ns) row.sent_ns = *a.now_ns; // force_encrypt, lib.rs:285
+}
+
+// no rows at all (nkeys == 0): every packet is rejected
+__global__ __launch_bounds__(256) void send_none_kernel(SendArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    rg_pkt_desc d = a.desc[i];
+    d.key_idx = RG_KEY_SKIP;
+    a.status[i] = RG_PKT_REJECTED;
+    a.counters_out[i] = 0;
+    if (a.rekey_out) a.rekey_out[i] = 0;
+    a.wdesc[i] = d;
+}
+
+// the verdicts of the packets that took no counter replace what the seal wrote for their RG_KEY_SKIP rows
+__global__ __launch_bounds__(256) void send_overlay_kernel(const uint8_t *verdict, uint8_t *status, uint32_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t v = verdict[i];
+    if (v != RG_PKT_PENDING) status[i] = v;
+}
+
+hipError_t launch_reserve(rg_send_state *state, uint32_t nkeys, const uint32_t *slots, const rg_pkt_desc *desc,
+                          uint32_t n, const uint64_t *now_ns, uint8_t *status, uint64_t *counters_out,
+                          uint8_t *rekey_out, uint8_t *ws, const SendLayout &L, hipStream_t st) {
+    SendArgs a{};
+    a.state = state;
+    a.slots = slots;
+    a.desc = desc;
+    a.now_ns = now_ns;
+    a.status = status;
+    a.counters_out = counters_out;
+    a.rekey_out = rekey_out;
+    a.wdesc = reinterpret_cast<rg_pkt_desc *>(ws + L.wdesc);
+    a.agg_val = reinterpret_cast<uint32_t *>(ws + L.agg_val);
+    a.agg_flag = reinterpret_cast<uint32_t *>(ws + L.agg_flag);
+    a.tot = reinterpret_cast<uint32_t *>(ws + L.tot);
+    a.nkeys = nkeys;
+    a.n = n;
+    a.nblk = L.nblk;
+    const dim3 per_packet((n + 255) / 256), tiles(L.nblk), wg(256);
+    if (nkeys == 0) {
+        hipLaunchKernelGGL(send_none_kernel, per_packet, wg, 0, st, a);
+        return hipGetLastError();
+    }
+    a.order = group_by_key(RowKey{slots, nkeys}, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
+                           reinterpret_cast<uint32_t *>(ws + L.order[0]), reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
+    hipLaunchKernelGGL(send_reduce_kernel, tiles, wg, 0, st, a);
+    hipLaunchKernelGGL(send_carry_kernel, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(send_verdict_kernel, tiles, wg, 0, st, a);
+    hipLaunchKernelGGL(send_update_kernel, per_packet, wg, 0, st, a);
+    return hipGetLastError();
+}
+
+} // namespace
+} // namespace rg
+
+extern "C" size_t rg_send_workspace_size(size_t n, uint32_t nkeys) { return (size_t)rg::send_layout(n, nkeys).total; }
+
+extern "C" int rg_send_reserve_batch_dev(rg_ctx *ctx, rg_send_state *state, uint32_t nkeys, const uint32_t *slots,
+                                         const rg_pkt_desc *desc, size_t n, const uint64_t *now_ns, uint8_t *status,
+                                         uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
+                                         size_t workspace_len, void *stream) {
+    rg::DeviceGuard dg_;
+    const int rc = rg::ctx_select(ctx);
+    if (rc) return rc;
+    if (n == 0) return RG_OK;
+    if (!state || !slots || !desc || !status || !counters_out || !workspace || n > 0xFFFFFFFFull)
+        return rg::api_error(RG_EINVAL, "send reserve: bad args");
+    if (((uintptr_t)state & 7u) || ((uintptr_t)workspace & 15u))
+        return rg::api_error(RG_EINVAL, "send reserve: state must be 8-byte and workspace 16-byte aligned");
+    const rg::SendLayout L = rg::send_layout(n, nkeys);
+    if (L.total == 0 || workspace_len < L.total)
+        return rg::api_error(RG_EINVAL, "send reserve: workspace smaller than rg_send_workspace_size");
+    const hipError_t e = rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, status, counters_out,
+                                            rekey_out, static_cast<uint8_t *>(workspace), L, (hipStream_t)stream);
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send reserve launch", e);
+    return RG_OK;
+}
+
+extern "C" int rg_send_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, const uint32_t *receivers, uint32_t nkeys,
+                                          rg_send_state *state, const uint32_t *slots, const rg_pkt_desc *desc,
+                                          size_t n, const uint64_t *now_ns, uint8_t *buf, size_t buf_len,
+                                          uint8_t *status, uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
+                                          size_t workspace_len, void *stream) {
+    rg::DeviceGuard dg_;
+    int rc = rg::ctx_select(ctx);
+    if (rc) return rc;
+    if (n == 0) return RG_OK;
+    if (!keys || !receivers || nkeys == 0 || !state || !slots || !desc || !buf || !status || !workspace ||
+        n > 0xFFFFFFFFull)
+        return rg::api_error(RG_EINVAL, "send resident: bad args");
+    if (((uintptr_t)state & 7u) || ((uintptr_t)workspace & 15u))
+        return rg::api_error(RG_EINVAL, "send resident: state must be 8-byte and workspace 16-byte aligned");
+    const rg::SendLayout L = rg::send_layout(n, nkeys);
+    if (L.total == 0 || workspace_len < L.total)
+        return rg::api_error(RG_EINVAL, "send resident: workspace smaller than rg_send_workspace_size");
+    hipStream_t st = (hipStream_t)stream;
+    rc = rg::ctx_claim_stream(ctx, st); // before any counter is taken
+    if (rc) return rc;
+    uint8_t *ws = static_cast<uint8_t *>(workspace);
+    uint8_t *verdict = ws + L.verdict;
+    uint64_t *ctr = counters_out ? counters_out : reinterpret_cast<uint64_t *>(ws + L.ctr);
+    hipError_t e = rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, verdict, ctr, rekey_out, ws, L, st);
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send resident: reserve launch", e);
+    // a packet that took no counter is RG_KEY_SKIP to the seal: no AEAD work, frame untouched
+    rc = rg_seal_batch_dev(ctx, keys, receivers, nkeys, reinterpret_cast<const rg_pkt_desc *>(ws + L.wdesc), ctr, n, buf,
+                           buf_len, status, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(rg::send_overlay_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
+                       (const uint8_t *)verdict, status, (uint32_t)n);
+    e = hipGetLastError();
+    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send resident: overlay launch", e);
+    return RG_OK;
+}

@@ -15,6 +15,11 @@
          fresh counters only, and 10 % replays of the previous batch.  Also written to
          profiles/replay_resident_bench.json
 
+  send   the device-frame send on cfg2 and cfg4 geometry (cfg4: 256 sessions interleaved in hash order, not sorted),
+         same plaintext, three ways in one run: (a) rg_seal_batch_dev with precomputed counters (the floor),
+         (b) rg_send_batch_dev (host wall clock: the host hands out the counters), (c) rg_send_batch_dev_resident.
+         Also written to profiles/send_resident_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -275,12 +280,101 @@ def replay_leg(eng):
     return res
 
 
+def send_leg(eng):
+    import time
+
+    T = 10**12
+
+    def shape(cfg):
+        w = workloads.build(cfg)
+        n, nk = w.n, len(w.receivers)
+        b = DeviceBatch(eng, w)
+        b.fill()
+        plain = b.buf.clone()
+        host_slots = np.ascontiguousarray(w.desc["key_idx"], np.uint32)  # cfg4: interleaved, not sorted
+        slots = torch.from_numpy(host_slots.view(np.int32).copy()).cuda()
+        tab = aead.Sessions(eng, nk)
+        tab.set_time(T)
+        keys = w.keys.reshape(-1, 32)
+        assert [tab.insert(0x70000000 + s, int(w.receivers[s]), keys[s].tobytes(), bytes(32)) for s in range(nk)] == \
+            list(range(nk))
+        tab.set_time(T + 5)
+        state0 = torch.from_numpy(np.tile(np.array([0, T, T], np.uint64), nk).view(np.int64)).cuda()
+        state = state0.clone()
+        now = torch.from_numpy(np.array([T + 5], np.uint64).view(np.int64)).cuda()
+        ws = eng.send_workspace(n, nk)
+        status_c = torch.zeros(n, dtype=torch.uint8, device="cuda")
+
+        def restore():
+            b.buf.copy_(plain)
+            state.copy_(state0)
+            for s in range(nk):
+                tab.set_send_counter(s, 0)
+            torch.cuda.synchronize()
+
+        def gpu_ms(fn):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            z.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(z)
+
+        def wall_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def floor():
+            b.seal()
+
+        def parent():
+            tab.send_batch_dev(host_slots, b.desc_seal, b.buf, b.status)
+
+        def resident():
+            eng.send_batch_dev_resident(b.keys, b.receivers, state, slots, b.desc_seal, b.buf, status_c, now_ns=now,
+                                        workspace=ws)
+
+        t = {"a_seal_gpu_ms": [], "b_parent_wall_ms": [], "c_resident_gpu_ms": [], "c_resident_wall_ms": []}
+        for rep in range(9):
+            restore()
+            t["a_seal_gpu_ms"].append(gpu_ms(floor))
+            restore()
+            t["b_parent_wall_ms"].append(wall_ms(parent))
+            frames_b = b.buf.clone()
+            restore()
+            t["c_resident_gpu_ms"].append(gpu_ms(resident))
+            assert torch.equal(status_c, b.status[:n]) and (status_c == 0).all().item(), "statuses disagree"
+            assert torch.equal(b.buf, frames_b), "resident and parent paths sealed different frames"
+            del frames_b
+            restore()
+            t["c_resident_wall_ms"].append(wall_ms(resident))
+        r = {k: {"median": round(float(np.median(v[2:])), 4), "min": round(min(v[2:]), 4), "max": round(max(v[2:]), 4)}
+             for k, v in t.items()}
+        r["c_over_a"] = round(r["c_resident_gpu_ms"]["median"] / r["a_seal_gpu_ms"]["median"], 3)
+        r["b_over_c"] = round(r["b_parent_wall_ms"]["median"] / r["c_resident_wall_ms"]["median"], 3)
+        return {"packets": n, "sessions": nk, **r}
+
+    res = {"cfg2": shape("cfg2"), "cfg4": shape("cfg4"),
+           "note": "9 alternating repetitions, the first two dropped; frames, device state rows and the session "
+                   "table's counters restored outside the timed region; (a) and (c) by stream events, (b) and (c) "
+                   "also by host wall clock around the call and a device sync; (b) and (c) sealed identical "
+                   "frames and statuses in every repetition"}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                        "send_resident_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
-                      ("replay", replay_leg)):
+                      ("replay", replay_leg), ("send", send_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
