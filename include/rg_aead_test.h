@@ -2,7 +2,8 @@
  * rg_aead_test.h -- test hooks of the MI355X WireGuard AEAD engine.
  *
  * Exported by the TEST library only (rustyguard_amd/lib/librg_aead_test.so: the product
- * kernels plus rg_api.cpp built with -DRG_TEST_HOOKS), never by the product library
+ * kernels plus the host units built with -DRG_TEST_HOOKS; the hooks themselves are
+ * rustyguard_amd/csrc/rg_debug.cpp), never by the product library
  * librg_aead.so, whose ABI is include/rg_aead.h.  The GPU tests that check key wiping
  * and allocation-failure paths load the test library beside the product one.
  */

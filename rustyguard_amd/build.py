@@ -1,14 +1,18 @@
 """Build librg_aead.so (HIP kernels + C ABI) in-tree for gfx950.
 
 ``python -m rustyguard_amd.build`` or ``__graft_entry__.build()``.  The .so files are
-git-ignored but travel to the GPU box with the gpurun snapshot.
+git-ignored.
 
 Two libraries come out of one set of kernel objects:
   lib/librg_aead.so       the product: include/rg_aead.h, no diagnostics, no test hooks
-  lib/librg_aead_test.so  the same kernels + rg_api.cpp with -DRG_TEST_HOOKS
-                          (include/rg_aead_test.h), loaded only by the GPU tests that
-                          check key wiping and allocation failures
+  lib/librg_aead_test.so  the same kernel objects + the host units (HOST) compiled a second
+                          time with -DRG_TEST_HOOKS (include/rg_aead_test.h), loaded only by the
+                          GPU tests that check key wiping and allocation failures
 Diagnostic builds (-DRG_DIAG: seal modes, per-wave stamps) are tools/build_variant.sh's.
+
+The source list lives here alone: ``python -m rustyguard_amd.build --list-sources`` prints every
+unit build() compiles, one file name per line (tools/build_variant.sh and tools/build_rev.sh loop
+over that output; tests/test_sanitize_cpu.py imports HOST).
 """
 from __future__ import annotations
 
@@ -25,9 +29,9 @@ LIB = os.path.join(LIBDIR, "librg_aead.so")
 TEST_LIB = os.path.join(LIBDIR, "librg_aead_test.so")
 KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip",
            "rg_replay.hip", "rg_send.hip"]
-API = "rg_api.cpp"
-SOURCES = KERNELS + [API]
-HEADERS = ["rg_device.h", "rg_internal.h", "rg_blake2s.h", "rg_radix.h"]
+HOST = ["rg_ctx.cpp", "rg_batch.cpp", "rg_hostpipe.cpp", "rg_message.cpp", "rg_sessions.cpp", "rg_debug.cpp"]
+SOURCES = KERNELS + HOST
+HEADERS = ["rg_device.h", "rg_internal.h", "rg_host.h", "rg_blake2s.h", "rg_radix.h"]
 ARCH = os.environ.get("RG_OFFLOAD_ARCH", "gfx950")
 # Per-file code generation.  The pipelined and flattened kernels run one wave per SIMD, so nothing hides a
 # hazard wait state: LLVM's iterative-ILP machine scheduler fills most of the s_nops the default strategy
@@ -76,15 +80,18 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     jobs = [(src, os.path.join(LIBDIR, src + ".o"), ()) for src in SOURCES]
-    jobs.append((API, os.path.join(LIBDIR, "rg_api_test.cpp.o"), ("-DRG_TEST_HOOKS=1",)))
+    jobs += [(src, os.path.join(LIBDIR, src + ".test.o"), ("-DRG_TEST_HOOKS=1",)) for src in HOST]
     # the largest kernel files take ~50 s each: compile them side by side
     with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
         objs = list(ex.map(lambda j: _compile(hipcc, j[0], j[1], j[2], verbose), jobs))
     kernel_objs = objs[:len(KERNELS)]
-    _link(hipcc, LIB, kernel_objs + [objs[len(KERNELS)]])
-    _link(hipcc, TEST_LIB, kernel_objs + [objs[-1]])
+    _link(hipcc, LIB, kernel_objs + objs[len(KERNELS):len(SOURCES)])
+    _link(hipcc, TEST_LIB, kernel_objs + objs[len(SOURCES):])
     return LIB
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--list-sources" in sys.argv:
+        print("\n".join(SOURCES))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

@@ -17,11 +17,12 @@
 // nearly every lane writes a reply, so that path is straight-line per lane.
 //
 // The entry point's host side is here too (argument checks, device guard,
-// launch): rg_api.cpp is also linked against a CPU stand-in of the launchers
-// (tests/sanitize) and so names no launcher of this file.
+// launch), on rg_host.h like the host units: those are also linked against a
+// CPU stand-in of the launchers (tests/sanitize) and so name no launcher of
+// this file.
 #include "rg_blake2s.h"
 #include "rg_device.h"
-#include "rg_internal.h"
+#include "rg_host.h"
 
 namespace rg {
 namespace {
@@ -132,16 +133,17 @@ extern "C" int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys
                                          const rg_src_addr *addrs, const uint8_t *overload, const uint8_t *nonces,
                                          size_t n, const uint8_t *buf, size_t buf_len, uint8_t *replies,
                                          uint8_t *status, void *stream) {
+    using namespace rg::host;
     rg::DeviceGuard dg_;
-    const int rc = rg::ctx_select(ctx);
+    const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!keys || !desc || !addrs || !nonces || !buf || !replies || !status || n > 0xFFFFFFFFull)
-        return rg::api_error(RG_EINVAL, "cookie reply: bad args");
+        return set_err(RG_EINVAL, "cookie reply: bad args");
     if (((uintptr_t)keys | (uintptr_t)replies) & 15u)
-        return rg::api_error(RG_EINVAL, "cookie reply: keys and replies must be 16-byte aligned");
+        return set_err(RG_EINVAL, "cookie reply: keys and replies must be 16-byte aligned");
     if (((uintptr_t)addrs | (uintptr_t)nonces) & 7u)
-        return rg::api_error(RG_EINVAL, "cookie reply: addrs and nonces must be 8-byte aligned");
+        return set_err(RG_EINVAL, "cookie reply: addrs and nonces must be 8-byte aligned");
     rg::CookieArgs a{};
     a.keys = reinterpret_cast<const uint32_t *>(keys);
     a.desc = desc;
@@ -154,7 +156,6 @@ extern "C" int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys
     a.status = status;
     a.n = (uint32_t)n;
     hipLaunchKernelGGL(rg::cookie_reply_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "cookie reply launch", e);
+    RG_HIP(hipGetLastError(), "cookie reply launch");
     return RG_OK;
 }

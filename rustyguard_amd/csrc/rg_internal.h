@@ -1,4 +1,4 @@
-// rg_internal.h -- declarations shared by the kernel TU and the C-ABI TU.
+// rg_internal.h -- declarations shared by the kernel files and the host units (rg_host.h builds on it).
 #pragma once
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -53,20 +53,20 @@ struct MacArgs {
 };
 hipError_t launch_mac_verify(const MacArgs &a, hipStream_t s);
 
-// An entry point that lives beside its kernel (rg_cookie_reply_batch_dev, rg_cookie.hip) reaches the
-// context through these two, defined in rg_api.cpp: rg_api.cpp itself then needs no launcher of that
-// kernel (it is also linked against a CPU stand-in for the launchers, tests/sanitize).
-// ctx_select: the null check and hipSetDevice of every entry point; RG_OK or the error, already recorded.
-int ctx_select(rg_ctx *ctx);
-// records the text rg_last_error() returns on this thread (with HIP's error string when e is one); returns code
-int api_error(int code, const char *what, hipError_t e = hipSuccess);
-// the one-stream rule of the device API (include/rg_aead.h) for an entry point that enqueues kernels of its
-// own ahead of rg_open_batch_dev / rg_seal_batch_dev: RG_OK, or RG_EINVAL (recorded) while the context's
-// last batch is still in flight on another stream.  An event query, no wait.
-int ctx_claim_stream(rg_ctx *ctx, hipStream_t st);
+// Lays a caller's workspace out (replay_layout below, send_layout in rg_send.hip): take(bytes) is the byte
+// offset of the next array from the 16-byte aligned base, each a multiple of 256; total() what was taken,
+// at least 256.
+struct WorkspaceCursor {
+    uint64_t at = 0;
+    uint64_t take(uint64_t bytes) {
+        const uint64_t o = at;
+        at += (bytes + 255) & ~255ull;
+        return o;
+    }
+    uint64_t total() const { return at ? at : 256; }
+};
 
-// Workspace of the device anti-replay calls (rg_replay.hip): byte offsets of its arrays from the caller's
-// 16-byte aligned base, each a multiple of 256.  total == 0: the batch is too large.
+// Workspace of the device anti-replay calls (rg_replay.hip).  total == 0: the batch is too large.
 constexpr uint32_t kReplayTile = 2048; // packets per workgroup of the scan and radix passes
 struct ReplayLayout {
     uint64_t rdesc; // [n] rg_pkt_desc: working descriptors of the open (RG_KEY_SKIP = unknown or gated); = 0
@@ -91,30 +91,25 @@ struct ReplayLayout {
 inline ReplayLayout replay_layout(uint64_t n, uint32_t nwin) {
     ReplayLayout L{};
     if (n > 0xFFFFFFFFull) return L; // total = 0
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 255) & ~255ull;
-        return o;
-    };
+    WorkspaceCursor ws;
     L.hash_cap = 64;
     while (L.hash_cap < 2 * n) L.hash_cap <<= 1;
     L.nblk = (uint32_t)((n + kReplayTile - 1) / kReplayTile);
     for (uint32_t top = nwin ? nwin - 1 : 0; top; top >>= 8) ++L.passes;
-    L.rdesc = take(n * sizeof(rg_pkt_desc));
-    L.hash = take(L.hash_cap * 4);
-    L.order[0] = take(L.passes > 0 ? n * 4 : 0);
-    L.order[1] = take(L.passes > 1 ? n * 4 : 0);
-    L.hist = take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
-    L.agg_val = take((uint64_t)L.nblk * 8);
-    L.agg_flag = take((uint64_t)L.nblk * 4);
-    L.lf = take(n * 8);
-    L.ctr = take(n * 8);
-    L.widx = take(n * 4);
-    L.undo = take(n);
-    L.ustatus = take(n);
-    L.udesc = take(n * sizeof(rg_pkt_desc));
-    L.total = at ? at : 256;
+    L.rdesc = ws.take(n * sizeof(rg_pkt_desc));
+    L.hash = ws.take(L.hash_cap * 4);
+    L.order[0] = ws.take(L.passes > 0 ? n * 4 : 0);
+    L.order[1] = ws.take(L.passes > 1 ? n * 4 : 0);
+    L.hist = ws.take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
+    L.agg_val = ws.take((uint64_t)L.nblk * 8);
+    L.agg_flag = ws.take((uint64_t)L.nblk * 4);
+    L.lf = ws.take(n * 8);
+    L.ctr = ws.take(n * 8);
+    L.widx = ws.take(n * 4);
+    L.undo = ws.take(n);
+    L.ustatus = ws.take(n);
+    L.udesc = ws.take(n * sizeof(rg_pkt_desc));
+    L.total = ws.total();
     return L;
 }
 
@@ -147,7 +142,7 @@ struct GeneralJob {
     uint32_t pad_;
 };
 
-// Launch geometry chosen by the host (rg_api.cpp): lanes per packet, CUs,
+// Launch geometry chosen by the host (rg_batch.cpp): lanes per packet, CUs,
 // resident 256-thread workgroups per CU (0 = plain one-shot grid).
 struct Launch {
     int lanes;
@@ -157,7 +152,7 @@ struct Launch {
     int staged_g;   // kernel family: 0 pipelined lanes (rg_pipe.hip), 1/2 LDS-staged tiles of that window (rg_tile.hip),
                     // 3 flattened chunk stream (rg_flat.hip)
     hipEvent_t done; // recorded by the transport kernel's own dispatch (hipExtLaunchKernel's stop event: no
-                     // extra queue packet; the device API's stream check, rg_api.cpp), or nullptr
+                     // extra queue packet; the device API's stream check, rg_host.h), or nullptr
 };
 
 // A transport launch, with its stop event when one is asked for: recorded as the kernel completes, by
@@ -343,7 +338,7 @@ __host__ __device__ __forceinline__ uint32_t rx_slot(uint32_t receiver, uint32_t
     return cap > 1 ? (receiver * 0x9E3779B1u) >> (32 - __builtin_ctz(cap)) : 0u;
 }
 hipError_t launch_general(GeneralJob *jobs, uint32_t njobs, uint8_t *arena, hipStream_t s);
-// device-resident session batches (rg_api.cpp): bind each packet to its key row; gather the
+// device-resident session batches (rg_sessions.cpp): bind each packet to its key row; gather the
 // frames the host's anti-replay pass rejected into a re-seal list (len W -> P = W - 32)
 hipError_t launch_bind_keys(const rg_pkt_desc *in, const uint32_t *key_idx, uint32_t n, rg_pkt_desc *out,
                             hipStream_t s);
@@ -352,7 +347,7 @@ hipError_t launch_undo_gather(const rg_pkt_desc *rd, const uint64_t *ctr, const 
 hipError_t launch_synth_fill(const rg_pkt_desc *desc, const uint32_t *inner_len, uint32_t n, uint8_t *buf,
                              uint64_t buf_len, uint64_t seed, hipStream_t s);
 
-// Control words of one planner (rg_api.cpp PlanBuf): the planner's class counts and finished-workgroup
+// Control words of one planner (rg_host.h PlanBuf): the planner's class counts and finished-workgroup
 // count, the pipelined kernel's schedule and the tile kernel's work pool, in one block that the preset
 // pass clears before every launch that hands work from one workgroup to another.
 constexpr uint32_t kCtlCounts = 0;   // [kClasses] class counts, [kClasses] finished planner / tile workgroups

@@ -31,10 +31,11 @@
 // DECRYPT_ERR, RG_PKT_PENDING included) rides along in window 0's group as a neutral element and comes
 // back untouched.
 //
-// The entry points' host side is here too (rg_cookie.hip's precedent): rg_api.cpp names no launcher of
-// this file.  All scratch is the caller's workspace; nothing is allocated, waited for or kept.
+// The entry points' host side is here too (rg_cookie.hip's precedent), on rg_host.h like the host units,
+// none of which names a launcher of this file.  All scratch is the caller's workspace; nothing is
+// allocated, waited for or kept.
 #include "rg_device.h"
-#include "rg_internal.h"
+#include "rg_host.h"
 #include "rg_radix.h"
 
 namespace rg {
@@ -421,20 +422,19 @@ extern "C" size_t rg_replay_workspace_size(size_t n, uint32_t nwin) { return (si
 extern "C" int rg_replay_batch_dev(rg_ctx *ctx, rg_antireplay *windows, uint32_t nwin, const uint32_t *win_idx,
                                    const uint64_t *counters, size_t n, uint8_t *status, uint8_t *undo,
                                    void *workspace, size_t workspace_len, void *stream) {
+    using namespace rg::host;
     rg::DeviceGuard dg_;
-    const int rc = rg::ctx_select(ctx);
+    int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!windows || !win_idx || !counters || !status || !workspace || n > 0xFFFFFFFFull)
-        return rg::api_error(RG_EINVAL, "replay: bad args");
-    if (((uintptr_t)windows & 7u) || ((uintptr_t)workspace & 15u))
-        return rg::api_error(RG_EINVAL, "replay: windows must be 8-byte and workspace 16-byte aligned");
+        return set_err(RG_EINVAL, "replay: bad args");
     const rg::ReplayLayout L = rg::replay_layout(n, nwin);
-    if (L.total == 0 || workspace_len < L.total)
-        return rg::api_error(RG_EINVAL, "replay: workspace smaller than rg_replay_workspace_size");
-    const hipError_t e = rg::launch_commit(windows, nwin, win_idx, counters, (uint32_t)n, status, undo,
-                                           static_cast<uint8_t *>(workspace), L, (hipStream_t)stream);
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "replay launch", e);
+    rc = check_workspace("replay", windows, workspace, workspace_len, L.total);
+    if (rc) return rc;
+    RG_HIP(rg::launch_commit(windows, nwin, win_idx, counters, (uint32_t)n, status, undo,
+                             static_cast<uint8_t *>(workspace), L, (hipStream_t)stream),
+           "replay launch");
     return RG_OK;
 }
 
@@ -443,20 +443,19 @@ extern "C" int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint
                                           const rg_pkt_desc *desc, size_t n, uint8_t *buf, size_t buf_len,
                                           uint8_t *status, uint64_t *counters_out, uint32_t *key_idx_out,
                                           void *workspace, size_t workspace_len, void *stream) {
+    using namespace rg::host;
     rg::DeviceGuard dg_;
-    int rc = rg::ctx_select(ctx);
+    int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!keys || nkeys == 0 || !rx_table || rx_cap == 0 || (rx_cap & (rx_cap - 1)) != 0 || !windows || !desc || !buf ||
         !status || !workspace || n > 0xFFFFFFFFull)
-        return rg::api_error(RG_EINVAL, "recv resident: bad args");
-    if (((uintptr_t)windows & 7u) || ((uintptr_t)workspace & 15u))
-        return rg::api_error(RG_EINVAL, "recv resident: windows must be 8-byte and workspace 16-byte aligned");
+        return set_err(RG_EINVAL, "recv resident: bad args");
     const rg::ReplayLayout L = rg::replay_layout(n, nkeys);
-    if (L.total == 0 || workspace_len < L.total)
-        return rg::api_error(RG_EINVAL, "recv resident: workspace smaller than rg_replay_workspace_size");
+    rc = check_workspace("recv resident", windows, workspace, workspace_len, L.total);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    rc = rg::ctx_claim_stream(ctx, st); // before anything is enqueued
+    rc = claim_stream(ctx, st); // before anything is enqueued
     if (rc) return rc;
     uint8_t *ws = static_cast<uint8_t *>(workspace);
     rg::ResidentArgs a{};
@@ -478,15 +477,13 @@ extern "C" int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint
     a.counters_out = counters_out;
     const dim3 grid((uint32_t)((n + 255) / 256)), wg(256);
     hipLaunchKernelGGL(rg::resident_gate_kernel, grid, wg, 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: gate launch", e);
+    RG_HIP(hipGetLastError(), "recv resident: gate launch");
     rc = rg_open_batch_dev(ctx, keys, nkeys, a.rdesc, n, buf, buf_len, status, counters_out, stream);
     if (rc) return rc;
-    e = rg::launch_commit(windows, nkeys, a.widx, a.ctr, (uint32_t)n, status, undo, ws, L, st);
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: commit launch", e);
+    RG_HIP(rg::launch_commit(windows, nkeys, a.widx, a.ctr, (uint32_t)n, status, undo, ws, L, st),
+           "recv resident: commit launch");
     hipLaunchKernelGGL(rg::resident_undo_kernel, grid, wg, 0, st, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "recv resident: undo launch", e);
+    RG_HIP(hipGetLastError(), "recv resident: undo launch");
     // re-seal under the same key row and counter: ciphertext and tag come back byte for byte; without
     // receivers the header is not rewritten (rg_recv_batch_dev_finish)
     return rg_seal_batch_dev(ctx, keys, nullptr, nkeys, a.udesc, a.ctr, n, buf, buf_len, ws + L.ustatus, stream);

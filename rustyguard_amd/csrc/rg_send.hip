@@ -26,10 +26,10 @@
 // A packet without a row (RG_KEY_SKIP, out of range) rides along in row 0's group, not eligible.
 // Plain vector stores only; no atomics on global memory.
 //
-// The entry points' host side is here too (rg_replay.hip's precedent).  All scratch is the caller's
-// workspace; nothing is allocated, waited for or kept.
+// The entry points' host side is here too (rg_replay.hip's precedent), on rg_host.h like the host units.
+// All scratch is the caller's workspace; nothing is allocated, waited for or kept.
 #include "rg_device.h"
-#include "rg_internal.h"
+#include "rg_host.h"
 #include "rg_radix.h"
 
 namespace rg {
@@ -38,8 +38,8 @@ namespace {
 constexpr uint64_t kRejectAfterTimeNs = 180ull * 1000000000ull; // REJECT_AFTER_TIME, lib.rs:204-209
 constexpr uint32_t kRounds = kRadixTile / 256;                  // rounds of 64 packets per wave
 
-// Workspace of the device send calls: byte offsets from the caller's 16-byte aligned base, each a multiple
-// of 256.  total == 0: the batch is too large.  Every term is non-decreasing in n and in nkeys.
+// Workspace of the device send calls (WorkspaceCursor, rg_internal.h).  total == 0: the batch is too large.
+// Every term is non-decreasing in n and in nkeys.
 struct SendLayout {
     uint64_t wdesc;    // [n] rg_pkt_desc: working descriptors (RG_KEY_SKIP = took no counter); = 0
     uint64_t order[2]; // [n] u32 each: packet indices grouped by row (ping-pong of the radix passes)
@@ -56,24 +56,19 @@ struct SendLayout {
 SendLayout send_layout(uint64_t n, uint32_t nkeys) {
     SendLayout L{};
     if (n > 0xFFFFFFFFull) return L;
-    uint64_t at = 0;
-    auto take = [&at](uint64_t bytes) {
-        const uint64_t o = at;
-        at += (bytes + 255) & ~255ull;
-        return o;
-    };
+    WorkspaceCursor ws;
     L.nblk = (uint32_t)((n + kRadixTile - 1) / kRadixTile);
     L.passes = radix_passes(nkeys);
-    L.wdesc = take(n * sizeof(rg_pkt_desc));
-    L.order[0] = take(L.passes > 0 ? n * 4 : 0);
-    L.order[1] = take(L.passes > 1 ? n * 4 : 0);
-    L.hist = take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
-    L.agg_val = take((uint64_t)L.nblk * 4);
-    L.agg_flag = take((uint64_t)L.nblk * 4);
-    L.tot = take(n * 4);
-    L.verdict = take(n);
-    L.ctr = take(n * 8);
-    L.total = at ? at : 256;
+    L.wdesc = ws.take(n * sizeof(rg_pkt_desc));
+    L.order[0] = ws.take(L.passes > 0 ? n * 4 : 0);
+    L.order[1] = ws.take(L.passes > 1 ? n * 4 : 0);
+    L.hist = ws.take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
+    L.agg_val = ws.take((uint64_t)L.nblk * 4);
+    L.agg_flag = ws.take((uint64_t)L.nblk * 4);
+    L.tot = ws.take(n * 4);
+    L.verdict = ws.take(n);
+    L.ctr = ws.take(n * 8);
+    L.total = ws.total();
     return L;
 }
 
@@ -352,20 +347,19 @@ extern "C" int rg_send_reserve_batch_dev(rg_ctx *ctx, rg_send_state *state, uint
                                          const rg_pkt_desc *desc, size_t n, const uint64_t *now_ns, uint8_t *status,
                                          uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
                                          size_t workspace_len, void *stream) {
+    using namespace rg::host;
     rg::DeviceGuard dg_;
-    const int rc = rg::ctx_select(ctx);
+    int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!state || !slots || !desc || !status || !counters_out || !workspace || n > 0xFFFFFFFFull)
-        return rg::api_error(RG_EINVAL, "send reserve: bad args");
-    if (((uintptr_t)state & 7u) || ((uintptr_t)workspace & 15u))
-        return rg::api_error(RG_EINVAL, "send reserve: state must be 8-byte and workspace 16-byte aligned");
+        return set_err(RG_EINVAL, "send reserve: bad args");
     const rg::SendLayout L = rg::send_layout(n, nkeys);
-    if (L.total == 0 || workspace_len < L.total)
-        return rg::api_error(RG_EINVAL, "send reserve: workspace smaller than rg_send_workspace_size");
-    const hipError_t e = rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, status, counters_out,
-                                            rekey_out, static_cast<uint8_t *>(workspace), L, (hipStream_t)stream);
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send reserve launch", e);
+    rc = check_workspace("send reserve", state, workspace, workspace_len, L.total);
+    if (rc) return rc;
+    RG_HIP(rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, status, counters_out, rekey_out,
+                              static_cast<uint8_t *>(workspace), L, (hipStream_t)stream),
+           "send reserve launch");
     return RG_OK;
 }
 
@@ -374,33 +368,31 @@ extern "C" int rg_send_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, cons
                                           size_t n, const uint64_t *now_ns, uint8_t *buf, size_t buf_len,
                                           uint8_t *status, uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
                                           size_t workspace_len, void *stream) {
+    using namespace rg::host;
     rg::DeviceGuard dg_;
-    int rc = rg::ctx_select(ctx);
+    int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!keys || !receivers || nkeys == 0 || !state || !slots || !desc || !buf || !status || !workspace ||
         n > 0xFFFFFFFFull)
-        return rg::api_error(RG_EINVAL, "send resident: bad args");
-    if (((uintptr_t)state & 7u) || ((uintptr_t)workspace & 15u))
-        return rg::api_error(RG_EINVAL, "send resident: state must be 8-byte and workspace 16-byte aligned");
+        return set_err(RG_EINVAL, "send resident: bad args");
     const rg::SendLayout L = rg::send_layout(n, nkeys);
-    if (L.total == 0 || workspace_len < L.total)
-        return rg::api_error(RG_EINVAL, "send resident: workspace smaller than rg_send_workspace_size");
+    rc = check_workspace("send resident", state, workspace, workspace_len, L.total);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    rc = rg::ctx_claim_stream(ctx, st); // before any counter is taken
+    rc = claim_stream(ctx, st); // before any counter is taken
     if (rc) return rc;
     uint8_t *ws = static_cast<uint8_t *>(workspace);
     uint8_t *verdict = ws + L.verdict;
     uint64_t *ctr = counters_out ? counters_out : reinterpret_cast<uint64_t *>(ws + L.ctr);
-    hipError_t e = rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, verdict, ctr, rekey_out, ws, L, st);
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send resident: reserve launch", e);
+    RG_HIP(rg::launch_reserve(state, nkeys, slots, desc, (uint32_t)n, now_ns, verdict, ctr, rekey_out, ws, L, st),
+           "send resident: reserve launch");
     // a packet that took no counter is RG_KEY_SKIP to the seal: no AEAD work, frame untouched
     rc = rg_seal_batch_dev(ctx, keys, receivers, nkeys, reinterpret_cast<const rg_pkt_desc *>(ws + L.wdesc), ctr, n, buf,
                            buf_len, status, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(rg::send_overlay_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
                        (const uint8_t *)verdict, status, (uint32_t)n);
-    e = hipGetLastError();
-    if (e != hipSuccess) return rg::api_error(RG_EDEVICE, "send resident: overlay launch", e);
+    RG_HIP(hipGetLastError(), "send resident: overlay launch");
     return RG_OK;
 }

@@ -1,4 +1,4 @@
-// driver.cpp -- TEST INFRASTRUCTURE ONLY: drives the host logic of rg_api.cpp (built host-only and linked
+// driver.cpp -- TEST INFRASTRUCTURE ONLY: drives the host logic of the host units (built host-only and linked
 // against tests/sanitize/hip_stub.cpp, no GPU) under AddressSanitizer + UBSan and under ThreadSanitizer
 // (tests/test_sanitize_cpu.py).  Every scenario checks its own results (seal -> open
 // round trips, forged frames, replayed counters, endpoints, fail-closed statuses) so a sanitizer run is

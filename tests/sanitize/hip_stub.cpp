@@ -1,5 +1,5 @@
 // hip_stub.cpp -- TEST INFRASTRUCTURE ONLY (tests/test_sanitize_cpu.py): a CPU stand-in for the parts of
-// the HIP runtime and of the kernel launchers that rg_api.cpp calls, so that the library's host logic --
+// the HIP runtime and of the kernel launchers that the host units call, so that the library's host logic --
 // the slice pipeline and its ordering, the group's worker threads, the splitter, the session layer's
 // anti-replay pass and side effects, the key-table wiping, the bounded waits -- can run under
 // AddressSanitizer / UndefinedBehaviorSanitizer and ThreadSanitizer on a machine without a GPU

@@ -93,7 +93,7 @@ def test_product_library_refuses_debug_modes(tmp_path):
     context-free path here (a null context is refused first) and on a real context by the GPU tests."""
     L = _lib.lib()
     assert L.rg_set_debug_mode(None, 0) == -1  # null context
-    src = open(os.path.join(REPO, "rustyguard_amd", "csrc", "rg_api.cpp")).read()
+    src = open(os.path.join(REPO, "rustyguard_amd", "csrc", "rg_ctx.cpp")).read()
     body = src[src.index("int rg_set_debug_mode("):]
     body = body[:body.index("\n}\n")]
     assert "#if RG_DIAG" in body and 'mode != 0) return set_err(RG_EINVAL' in body

@@ -1,7 +1,8 @@
 """The library's host logic under AddressSanitizer + UBSan and ThreadSanitizer, on the CPU.
 
-rg_api.cpp is compiled host-only (hipcc --cuda-host-only, the sanitizer flags after -Xarch_host) and linked
-against tests/sanitize/hip_stub.cpp -- a CPU stand-in for the HIP runtime calls it makes and for the kernel
+Every host unit (rustyguard_amd.build.HOST) is compiled host-only (hipcc --cuda-host-only, the sanitizer flags
+after -Xarch_host) and linked
+against tests/sanitize/hip_stub.cpp -- a CPU stand-in for the HIP runtime calls they make and for the kernel
 launchers, with the kernels' descriptor checks and status rules around a fake cipher -- and driven by
 tests/sanitize/driver.cpp: the host slice pipeline with descriptors out of offset order, the session layer's
 replay pass and side effects, a four-context group whose batches start one worker thread per context, the
@@ -15,6 +16,7 @@ import subprocess
 import pytest
 
 from conftest import REPO
+from rustyguard_amd.build import CSRC, HOST
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
@@ -31,9 +33,9 @@ def _build(kind, out):
     for fl in f:
         host += ["-Xarch_host", fl]
     objs = []
-    jobs = [(host + ["-DRG_TEST_HOOKS=1"] + inc, os.path.join(REPO, "rustyguard_amd", "csrc", "rg_api.cpp")),
-            (host + inc, os.path.join(SAN, "hip_stub.cpp")),
-            ([CLANG, "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer"] + f + inc, os.path.join(SAN, "driver.cpp"))]
+    jobs = [(host + ["-DRG_TEST_HOOKS=1"] + inc, os.path.join(CSRC, src)) for src in HOST]
+    jobs += [(host + inc, os.path.join(SAN, "hip_stub.cpp")),
+             ([CLANG, "-O1", "-g", "-std=c++17", "-fno-omit-frame-pointer"] + f + inc, os.path.join(SAN, "driver.cpp"))]
     procs = []
     for cmd, src in jobs:
         o = os.path.join(out, os.path.basename(src) + f".{kind}.o")

@@ -13,8 +13,13 @@ sched=()
 grep -q "iterative-ilp" "$src/rustyguard_amd/build.py" && sched=(-mllvm -amdgpu-sched-strategy=iterative-ilp)
 mkdir -p tools/build
 objs=()
-for s in rg_kernels.hip rg_tile.hip rg_pipe.hip rg_flat.hip rg_mac.hip rg_cookie.hip rg_api.cpp; do
-    [[ -f "$src/rustyguard_amd/csrc/$s" ]] || continue # a file that revision does not have yet
+# that revision's own units: its build.py's --list-sources, or its SOURCES where it predates the option
+if grep -q -- "--list-sources" "$src/rustyguard_amd/build.py"; then
+    list=$(python3 "$src/rustyguard_amd/build.py" --list-sources)
+else
+    list=$(cd "$src/rustyguard_amd" && python3 -c "import build; print('\n'.join(build.SOURCES))")
+fi
+for s in $list; do
     x=()
     [[ $s == *.cpp ]] && x=(-x hip)
     [[ $s == rg_pipe.hip || $s == rg_flat.hip ]] && x+=("${sched[@]}")

@@ -10,7 +10,7 @@ shift
 out=tools/build/var_$name
 mkdir -p "$out"
 objs=()
-for src in rg_kernels.hip rg_tile.hip rg_pipe.hip rg_flat.hip rg_mac.hip rg_cookie.hip rg_api.cpp; do
+for src in $(python3 -m rustyguard_amd.build --list-sources); do # the product's units, kernels and host
     x=()
     [[ $src == *.cpp ]] && x=(-x hip)
     extra=("$@")
