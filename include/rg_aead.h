@@ -91,6 +91,8 @@ enum rg_pkt_status {
                                error, or a batch still in flight).  Never an accept. */
     RG_PKT_COOKIE = 7,      /* rg_cookie_reply_batch_dev: mac1 valid, mac2 missing or wrong while overloaded;
                                a cookie reply was written for this message */
+    RG_PKT_KEYEXCHANGE = 8, /* Error::KeyExchangeError: an X25519 result was all zero (rg_x25519_batch_dev and
+                               the handshake calls) */
 };
 
 /* Statuses fail closed.  A packet reads RG_PKT_OK only after the kernel that processed it wrote that
@@ -236,6 +238,106 @@ int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys, const rg_
                               const uint8_t *nonces /* [n][24], caller's CSPRNG output */, size_t n,
                               const uint8_t *buf, size_t buf_len, uint8_t *replies /* [n][64], 16-byte aligned */,
                               uint8_t *status, void *stream);
+
+/* ------------------------------ Noise IKpsk2 responder (batch, async) */
+/* The step behind the filter above: Sessions::handle_handshake_init's cryptography (rustyguard-core/src/
+ * handshake.rs:36-137) for every message the filter passed, without a host step per message.  All pointers
+ * are device memory unless marked host; the calls enqueue on `stream` and return without waiting, keep
+ * nothing in the context (so they may run on any stream and be captured into a graph) and never write buf.
+ * n == 0 returns RG_OK; RG_EINVAL with nothing enqueued for a null required pointer, n > 2^32 - 1 or a
+ * misaligned array (each call names its rule).
+ *
+ * rg_x25519_batch_dev is CryptoPrimatives::x25519 / x25519_pubkey (prim.rs:79-80, :159-177) for n rows, one
+ * lane per row: out[i] = X25519(scalars[i], points[i]) as RFC 7748 §5 defines it (the scalar is clamped, bit
+ * 255 of the point is masked, non-canonical points are accepted); points == NULL means the base point 9.
+ * status[i] is RG_PKT_OK, or RG_PKT_KEYEXCHANGE when the result is all zero, in which case out[i] is 32 zero
+ * bytes.  The all-zero result (RFC 7748 §6.1: a point of small order) is X25519's only failure and the only
+ * one reported here; what else the reference's library (graviola, not available to this project) might
+ * refuse in diffie_hellman is not known.  Constant time: no branch and no address depends on a scalar or a
+ * result.  Rows must be 4-byte aligned. */
+int rg_x25519_batch_dev(rg_ctx *ctx, const uint8_t *scalars /* [n][32] */,
+                        const uint8_t *points /* [n][32], or NULL = the base point 9 */,
+                        uint8_t *out /* [n][32] */, uint8_t *status /* [n] */, size_t n, void *stream);
+
+typedef struct rg_hs_static {        /* 64 bytes, 16-byte aligned: StaticInitiatorConfig */
+    uint8_t private_key[32];
+    uint8_t public_key[32];          /* X25519(private_key, 9) */
+} rg_hs_static;
+
+typedef struct rg_hs_peer {          /* 96 bytes, 16-byte aligned rows: StaticPeerConfig */
+    uint8_t public_key[32];
+    uint8_t preshared_key[32];       /* zero when the peer has none */
+    uint8_t mac1_key[32];            /* mac1_key(public_key), lib.rs:72-74 */
+} rg_hs_peer;
+
+typedef struct rg_hs_init_result {   /* 128 bytes, 16-byte aligned */
+    uint8_t chain[32], hash[32];     /* HandshakeState after the initiation */
+    uint8_t ephemeral[32];           /* the initiator's ephemeral public key (msg[8..40]) */
+    uint8_t timestamp[12];           /* decrypted TAI64N */
+    uint32_t peer;                   /* row of peers, RG_PEER_NONE unless status is RG_PKT_OK */
+    uint32_t sender;                 /* msg[4..8] */
+    uint8_t pad[12];
+} rg_hs_init_result;
+
+/* Config::get_peer_idx as an open-addressing table over peer rows, built on the host and read on the
+ * device: table[slot] is a row of peers or 0xFFFFFFFF (empty), slot = (le32(public_key[0..4]) * 0x9E3779B1)
+ * >> (32 - log2 cap), linear probing; cap a power of two >= 2 npeers.  A duplicate public key is RG_EINVAL.
+ * The key comparison reads all 32 bytes with no early exit.  Host pointers.  rg_peer_table_find: the row of
+ * pk, or -1. */
+int rg_peer_table_build(const rg_hs_peer *peers, uint32_t npeers, uint32_t *table, uint32_t cap);
+int64_t rg_peer_table_find(const rg_hs_peer *peers, const uint32_t *table, uint32_t cap, const uint8_t pk[32]);
+
+/* rg_handshake_init_batch_dev: decrypt_handshake_init (rustyguard-crypto/src/lib.rs:346-384) and
+ * Config::get_peer_idx for n messages.  desc[i]: offset, len = whole message.  Per message, in the
+ * reference's order:
+ *   offset % 16 != 0                                   RG_PKT_UNALIGNED
+ *   frame outside [buf, buf + buf_len), or len != 148  RG_PKT_INVALID
+ *   gate && gate[i] != RG_PKT_OK, or
+ *   key_idx == RG_KEY_SKIP                             RG_PKT_REJECTED, message not read
+ *   type word != 1                                     RG_PKT_INVALID
+ *   X25519(own.private_key, ephemeral) all zero        RG_PKT_KEYEXCHANGE
+ *   the encrypted static key's tag fails               RG_PKT_DECRYPT_ERR
+ *   X25519(own.private_key, decrypted static) all zero RG_PKT_KEYEXCHANGE
+ *   the encrypted timestamp's tag fails                RG_PKT_DECRYPT_ERR
+ *   the static key is not in the table                 RG_PKT_REJECTED (after both fields opened, as
+ *                                                      handshake.rs:75-82)
+ *   otherwise                                          RG_PKT_OK, results[i] filled
+ * gate lets rg_cookie_reply_batch_dev's status array feed this call on the same stream with no host step.
+ * mac1 and mac2 are NOT checked here: run the filter first.  The row of every message whose status is not
+ * RG_PKT_OK is written as 128 zero bytes with peer = RG_PEER_NONE, so no partial secret state is left
+ * behind; a lane stores its status after its row.  The timestamp-replay check (peer.latest_ts,
+ * handshake.rs:88-91) is an in-order pass per peer and stays with the caller, which reads results[i].
+ * timestamp and .peer before it lets a row on to the response (clear its gate byte otherwise).
+ * RG_EINVAL also for cap not a power of two; own, peers, desc and results must be 16-byte aligned,
+ * peer_table 4-byte aligned. */
+int rg_handshake_init_batch_dev(rg_ctx *ctx, const rg_hs_static *own, const rg_hs_peer *peers, uint32_t npeers,
+                                const uint32_t *peer_table, uint32_t cap, const rg_pkt_desc *desc,
+                                const uint8_t *gate /* [n] or NULL */, size_t n, const uint8_t *buf, size_t buf_len,
+                                rg_hs_init_result *results, uint8_t *status, void *stream);
+
+/* rg_handshake_resp_batch_dev: encrypt_handshake_resp (lib.rs:386-433) and HandshakeState::split(false)
+ * (prim.rs:299-313) for n result rows.  Per row:
+ *   gate && gate[i] != RG_PKT_OK      RG_PKT_REJECTED; nothing of the row is read or written
+ *   results[i].peer >= npeers         RG_PKT_INVALID
+ *   the ee or se secret all zero      RG_PKT_KEYEXCHANGE
+ *   otherwise                         RG_PKT_OK: responses[i] = the 92-byte HandshakeResp
+ *       le32(2) || session_ids[i] || results[i].sender || X25519(esk[i], 9) || tag(16) || mac1 || mac2
+ *     (4 zero bytes behind it), mac1 under peers[peer].mac1_key over bytes 0..60, mac2 under cookies[i]
+ *     over bytes 0..76 when cookies && has_cookie[i], else zero; transport_keys[i] = send key || receive
+ *     key, the order rg_sessions_insert takes them (send = HKDF's second output, receive = the new chain).
+ * On any failure the response row and the key row are zero.  results[i].chain and .hash are zeroed by every
+ * row that was not gated off (HandshakeState::zeroize): a row is consumed once.
+ * Randomness: the library has no RNG.  esk[i] must be 32 fresh bytes of the caller's CSPRNG for every row
+ * of every call (EphemeralPrivateKey::generate, handshake.rs:98), never reused; session_ids[i] is the
+ * caller's session index (allocate_session!).  peers, results, responses and transport_keys must be
+ * 16-byte aligned, esk, session_ids and cookies 4-byte aligned; has_cookie is required with cookies. */
+int rg_handshake_resp_batch_dev(rg_ctx *ctx, const rg_hs_peer *peers, uint32_t npeers, rg_hs_init_result *results,
+                                const uint8_t *gate /* [n] or NULL */, const uint8_t *esk /* [n][32] */,
+                                const uint32_t *session_ids /* [n] */, const uint8_t *cookies /* [n][16] or NULL */,
+                                const uint8_t *has_cookie /* [n], required with cookies */, size_t n,
+                                uint8_t *responses /* [n][96], 16-byte aligned, 92 bytes used */,
+                                uint8_t *transport_keys /* [n][64]: send key || receive key */,
+                                uint8_t *status, void *stream);
 
 /* Tuning knobs.  lanes: lanes cooperating on one packet (0 = automatic, else
  * 1/2/4).  wg_per_cu: resident 256-thread workgroups per CU of the persistent

@@ -38,6 +38,13 @@ SIGNATURES = {
                                         c_size, c_vp, c_vp, c_vp]),
     "rg_cookie_reply_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_size, c_vp, c_vp,
                                           c_vp]),
+    "rg_x25519_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_peer_table_build": (c_int, [c_vp, c_u32, c_vp, c_u32]),
+    "rg_peer_table_find": (ctypes.c_int64, [c_vp, c_vp, c_u32, c_vp]),
+    "rg_handshake_init_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_size,
+                                            c_vp, c_vp, c_vp]),
+    "rg_handshake_resp_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp,
+                                            c_vp, c_vp]),
     "rg_rx_table_build": (c_int, [c_vp, c_vp, c_size, c_vp, ctypes.c_uint32]),
     "rg_rx_table_find": (ctypes.c_int64, [c_vp, ctypes.c_uint32, ctypes.c_uint32]),
     "rg_open_batch_dev_rx": (c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, ctypes.c_uint32, c_vp, c_size, c_vp, c_size,

@@ -31,6 +31,8 @@ from .workloads import DESC_DTYPE
 
 PKT_OK, PKT_DECRYPT_ERR, PKT_INVALID, PKT_REJECTED, PKT_UNALIGNED, PKT_NOT_DATA, PKT_PENDING = range(7)
 PKT_COOKIE = 7  # rg_cookie_reply_batch_dev: a cookie reply was written for this message
+PKT_KEYEXCHANGE = 8  # Error::KeyExchangeError: an all-zero X25519 result (x25519_dev, the handshake calls)
+PEER_NONE = 0xFFFFFFFF
 RECV_AUTHENTICATED, RECV_KEEPALIVE = 1, 2
 KEY_SCAN = 0xFFFFFFFE  # rg_mac_verify_batch_dev: try every key
 KEY_SKIP = 0xFFFFFFFF
@@ -220,6 +222,45 @@ class Engine:
                                                       _vp(nonces), n, _vp(buf), _nbytes(buf), _vp(replies),
                                                       _vp(status), _stream_handle(stream)),
                     "rg_cookie_reply_batch_dev")
+
+    def x25519_dev(self, scalars, points, out, status, stream=None):
+        """CryptoPrimatives::x25519 / x25519_pubkey for a batch (rg_x25519_batch_dev): scalars, points and out
+        are 32 bytes per row; points = None means the base point.  status: PKT_OK, or PKT_KEYEXCHANGE for an
+        all-zero result (out[i] is then zero)."""
+        n = _nbytes(status)
+        assert _nbytes(scalars) >= 32 * n and _nbytes(out) >= 32 * n and (points is None or _nbytes(points) >= 32 * n)
+        self._check(self._L.rg_x25519_batch_dev(self._h, _vp(scalars), _vp(points), _vp(out), _vp(status), n,
+                                                _stream_handle(stream)), "rg_x25519_batch_dev")
+
+    def handshake_init_dev(self, own, peers, table, desc, gate, buf, results, status, stream=None):
+        """decrypt_handshake_init + Config::get_peer_idx for a batch of initiations
+        (rg_handshake_init_batch_dev): own = one rg_hs_static (64 bytes), peers = rg_hs_peer rows (96 bytes),
+        table = peer_table(peers) on the device, gate = one status byte per message (e.g. cookie_reply_dev's
+        output) or None, results = 128 bytes per message.  mac1 / mac2 are not checked here."""
+        n = _ndesc(desc)
+        assert _nbytes(own) == 64 and _nbytes(peers) % 96 == 0 and _nbytes(results) >= 128 * n
+        assert _nbytes(status) >= n and (gate is None or _nbytes(gate) >= n)
+        self._check(self._L.rg_handshake_init_batch_dev(self._h, _vp(own), _vp(peers), _nbytes(peers) // 96,
+                                                        _vp(table), _nbytes(table) // 4, _vp(desc), _vp(gate), n,
+                                                        _vp(buf), _nbytes(buf), _vp(results), _vp(status),
+                                                        _stream_handle(stream)), "rg_handshake_init_batch_dev")
+
+    def handshake_resp_dev(self, peers, results, gate, esk, session_ids, cookies, has_cookie, responses,
+                           transport_keys, status, stream=None):
+        """encrypt_handshake_resp + split(false) for the result rows of handshake_init_dev
+        (rg_handshake_resp_batch_dev): esk = 32 fresh bytes of the caller's CSPRNG per row, session_ids = uint32
+        per row, cookies = 16 bytes per row with has_cookie = one byte per row (or both None), responses = 96
+        bytes per row (92 used), transport_keys = 64 bytes per row (send key || receive key).  The rows'
+        chain and hash are zeroed."""
+        n = _nbytes(status)
+        assert _nbytes(results) >= 128 * n and _nbytes(esk) >= 32 * n and _nbytes(session_ids) >= 4 * n
+        assert _nbytes(responses) >= 96 * n and _nbytes(transport_keys) >= 64 * n
+        assert (cookies is None and has_cookie is None) or (_nbytes(cookies) >= 16 * n and _nbytes(has_cookie) >= n)
+        self._check(self._L.rg_handshake_resp_batch_dev(self._h, _vp(peers), _nbytes(peers) // 96, _vp(results),
+                                                        _vp(gate), _vp(esk), _vp(session_ids), _vp(cookies),
+                                                        _vp(has_cookie), n, _vp(responses), _vp(transport_keys),
+                                                        _vp(status), _stream_handle(stream)),
+                    "rg_handshake_resp_batch_dev")
 
     def replay_workspace(self, n: int, nwin: int, device=None):
         """The scratch tensor (uint8, on this engine's device) that replay_batch_dev / recv_batch_dev_resident
@@ -740,6 +781,26 @@ def rx_table(receivers, key_idx, cap: int | None = None) -> np.ndarray:
 def rx_find(table: np.ndarray, receiver: int) -> int:
     """Host lookup in an rx_table(): key index or -1."""
     return int(lib().rg_rx_table_find(_vp(table), table.shape[0], receiver))
+
+
+def peer_table(peers: np.ndarray, cap: int | None = None) -> np.ndarray:
+    """Peer table for handshake_init_dev (rg_peer_table_build) over rg_hs_peer rows (uint8 [npeers, 96]: public
+    key, preshared key, mac1 key): uint32 [cap] of peer rows, 0xFFFFFFFF = empty, cap a power of two >= 2 npeers
+    (default: the smallest)."""
+    rows = np.ascontiguousarray(peers, np.uint8).reshape(-1, 96)
+    if cap is None:
+        cap = 1 << max(1, int(2 * len(rows) - 1).bit_length())
+    table = np.zeros(cap, np.uint32)
+    check(lib().rg_peer_table_build(_vp(rows), len(rows), _vp(table), cap), "rg_peer_table_build")
+    return table
+
+
+def peer_find(peers: np.ndarray, table: np.ndarray, public_key: bytes) -> int:
+    """Host lookup in a peer_table(): the peer's row or -1."""
+    rows = np.ascontiguousarray(peers, np.uint8).reshape(-1, 96)
+    pk = np.frombuffer(bytes(public_key), np.uint8)
+    assert pk.size == 32
+    return int(lib().rg_peer_table_find(_vp(rows), _vp(table), table.shape[0], _vp(pk)))
 
 
 def numa_node(engine) -> int:

@@ -251,6 +251,45 @@ int64_t rg_rx_table_find(const rg_rx_entry *table, uint32_t cap, uint32_t receiv
     return -1;
 }
 
+// Config::get_peer_idx as a table over peer rows (rg_handshake.hip reads it): the receiver table's slot rule
+// on the public key's first word.  Keys are compared over all 32 bytes, without an early exit.
+static uint32_t peer_key_diff(const uint8_t *a, const uint8_t *b) {
+    uint32_t diff = 0;
+    for (int i = 0; i < 32; ++i) diff |= (uint32_t)(a[i] ^ b[i]);
+    return diff;
+}
+
+static uint32_t peer_key_word(const uint8_t *pk) {
+    return (uint32_t)pk[0] | ((uint32_t)pk[1] << 8) | ((uint32_t)pk[2] << 16) | ((uint32_t)pk[3] << 24);
+}
+
+int rg_peer_table_build(const rg_hs_peer *peers, uint32_t npeers, uint32_t *table, uint32_t cap) {
+    if (!table || (npeers && !peers)) return set_err(RG_EINVAL, "peer table: null pointer");
+    if (cap == 0 || (cap & (cap - 1)) != 0 || (uint64_t)cap < 2ull * npeers)
+        return set_err(RG_EINVAL, "peer table: cap must be a power of two >= 2 npeers");
+    for (uint32_t s = 0; s < cap; ++s) table[s] = RG_PEER_NONE;
+    for (uint32_t i = 0; i < npeers; ++i) {
+        uint32_t s = rg::rx_slot(peer_key_word(peers[i].public_key), cap);
+        while (table[s] != RG_PEER_NONE) {
+            if (peer_key_diff(peers[table[s]].public_key, peers[i].public_key) == 0)
+                return set_err(RG_EINVAL, "peer table: duplicate public key");
+            s = (s + 1) & (cap - 1);
+        }
+        table[s] = i;
+    }
+    return RG_OK;
+}
+
+int64_t rg_peer_table_find(const rg_hs_peer *peers, const uint32_t *table, uint32_t cap, const uint8_t pk[32]) {
+    if (!peers || !table || !pk || cap == 0 || (cap & (cap - 1)) != 0) return -1;
+    uint32_t s = rg::rx_slot(peer_key_word(pk), cap);
+    for (uint32_t probe = 0; probe < cap && table[s] != RG_PEER_NONE; ++probe) {
+        if (peer_key_diff(peers[table[s]].public_key, pk) == 0) return table[s];
+        s = (s + 1) & (cap - 1);
+    }
+    return -1;
+}
+
 int rg_open_batch_dev_rx(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys, const rg_rx_entry *rx_table,
                          uint32_t rx_cap, const rg_pkt_desc *desc, size_t n, uint8_t *buf, size_t buf_len,
                          uint8_t *status, uint64_t *counters_out, uint32_t *key_idx_out, void *stream) {

@@ -111,4 +111,94 @@ __device__ __forceinline__ uint4 b2s_mac16(const uint32_t ks[8], const uint8_t *
     return make_uint4(h[0], h[1], h[2], h[3]);
 }
 
+// ------------------------------------------------ the handshake's hash, HMAC and HKDF (rg_handshake.hip)
+// Core::blake2s_hash, hmac_blake2s and hkdf_blake2s (prim.rs:41-72, :116-157) on words, for the lengths the
+// IKpsk2 transcript has.  Lengths and output counts are run-time values so that one call site serves
+// several steps of the handshake (the compression function is ~1100 instructions per site); none of them
+// depends on a secret.
+
+// unkeyed BLAKE2s with a 32-byte digest: the parameter block alone
+__device__ __forceinline__ void b2s_init32(uint32_t h[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = kIV[i];
+    h[0] ^= 0x01010020u;
+}
+
+// out = BLAKE2s-256(a || b) for a 32-byte a and nbw <= 12 words of b (words of b past nbw must be zero):
+// HandshakeState::mix_hash.  One block up to 64 bytes in all, else two.
+__device__ __forceinline__ void b2s_hash32(const uint32_t a[8], const uint32_t b[12], uint32_t nbw, uint32_t out[8]) {
+    uint32_t h[8], m[16];
+    b2s_init32(h);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        m[i] = a[i];
+        m[8 + i] = b[i];
+    }
+    const bool two = nbw > 8;
+    b2s_compress(h, m, two ? 64u : 32u + 4u * nbw, !two);
+    if (two) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m[i] = i < 4 ? b[8 + i] : 0u;
+        b2s_compress(h, m, 32u + 4u * nbw, true);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] = h[i];
+}
+
+// out = HMAC-BLAKE2s(key, msg) for a 32-byte key and len <= 33 message bytes in m[9] (zero past len).  The
+// two passes (ipad, opad) share their code; an empty message makes the pad block the hash's only block.
+__device__ __forceinline__ void b2s_hmac(const uint32_t key[8], const uint32_t m[9], uint32_t len, uint32_t out[8]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const uint32_t pad = pass ? 0x5C5C5C5Cu : 0x36363636u;
+        const uint32_t mlen = pass ? 32u : len;
+        uint32_t h[8], blk[16];
+        b2s_init32(h);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            blk[i] = key[i] ^ pad;
+            blk[8 + i] = pad;
+        }
+        b2s_compress(h, blk, 64, mlen == 0);
+        if (mlen != 0) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) blk[i] = i < 8 ? (pass ? out[i] : m[i]) : (i == 8 && !pass) ? m[8] : 0u;
+            b2s_compress(h, blk, 64 + mlen, true);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[i] = h[i]; // the inner digest after pass 0, the MAC after pass 1
+    }
+}
+
+// hkdf_blake2s (prim.rs:145-157): chain = T(1), o1 = T(2), o2 = T(3) of HKDF(chain, msg) for nout = 0, 1 or 2
+// further outputs (mix_chain, mix_key, mix_key_and_hash; split with an empty msg).  msg: len = 0 or 32 bytes.
+__device__ __forceinline__ void b2s_hkdf(uint32_t chain[8], const uint32_t msg[8], uint32_t len, uint32_t nout,
+                                         uint32_t o1[8], uint32_t o2[8]) {
+    uint32_t key[8], m[9], t[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        key[i] = chain[i];
+        m[i] = len ? msg[i] : 0u;
+    }
+    m[8] = 0;
+    uint32_t mlen = len;
+#pragma unroll 1
+    for (uint32_t step = 0; step <= nout + 1; ++step) { // step 0: the PRK; step i: T(i) = HMAC(PRK, T(i-1) || i)
+        b2s_hmac(key, m, mlen, t);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (step == 0) key[i] = t[i];
+            if (step == 1) chain[i] = t[i];
+            if (step == 2) o1[i] = t[i];
+            if (step == 3) o2[i] = t[i];
+            m[i] = step == 0 ? 0u : t[i];
+        }
+        m[0] = step == 0 ? 1u : m[0];
+        m[8] = step == 0 ? 0u : step + 1;
+        mlen = step == 0 ? 1u : 33u;
+    }
+}
+
 } // namespace rg

@@ -20,6 +20,11 @@
          (b) rg_send_batch_dev (host wall clock: the host hands out the counters), (c) rg_send_batch_dev_resident.
          Also written to profiles/send_resident_bench.json
 
+  handshake  the batched IKpsk2 responder at 64 Ki and 1 Ki rows (256 distinct valid initiations, tiled):
+         rg_x25519_batch_dev alone, rg_handshake_init_batch_dev, rg_handshake_resp_batch_dev and both as
+         handshakes/s, by stream events, medians of seven with min-max; OpenSSL's X25519 through libcrypto on 1
+         and 16 threads beside it when the library is there.  Also written to profiles/handshake_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -369,12 +374,158 @@ def send_leg(eng):
     return res
 
 
+def _openssl_x25519(seconds=1.0):
+    """OpenSSL's X25519 through libcrypto (ctypes releases the GIL, so threads run side by side): derivations
+    per second on 1 and 16 threads, or None when the library is not there."""
+    import ctypes
+    import ctypes.util
+    import threading
+    import time
+
+    name = ctypes.util.find_library("crypto")
+    if not name:
+        return None
+    try:
+        C = ctypes.CDLL(name)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        C.EVP_PKEY_new_raw_private_key.restype = vp
+        C.EVP_PKEY_new_raw_private_key.argtypes = [ctypes.c_int, vp, ctypes.c_char_p, sz]
+        C.EVP_PKEY_new_raw_public_key.restype = vp
+        C.EVP_PKEY_new_raw_public_key.argtypes = [ctypes.c_int, vp, ctypes.c_char_p, sz]
+        C.EVP_PKEY_CTX_new.restype = vp
+        C.EVP_PKEY_CTX_new.argtypes = [vp, vp]
+        C.EVP_PKEY_derive_init.argtypes = [vp]
+        C.EVP_PKEY_derive_set_peer.argtypes = [vp, vp]
+        C.EVP_PKEY_derive.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(sz)]
+        C.EVP_PKEY_CTX_free.argtypes = [vp]
+        C.EVP_PKEY_free.argtypes = [vp]
+    except (OSError, AttributeError):
+        return None
+    NID_X25519 = 1034
+
+    def worker(count, stop):
+        sk = C.EVP_PKEY_new_raw_private_key(NID_X25519, None, os.urandom(32), 32)
+        pk = C.EVP_PKEY_new_raw_public_key(NID_X25519, None, bytes([9]) + bytes(31), 32)
+        out, n = ctypes.create_string_buffer(32), 0
+        while not stop.is_set():
+            ctx = C.EVP_PKEY_CTX_new(sk, None)
+            ln = sz(32)
+            ok = C.EVP_PKEY_derive_init(ctx) == 1 and C.EVP_PKEY_derive_set_peer(ctx, pk) == 1 and \
+                C.EVP_PKEY_derive(ctx, out, ctypes.byref(ln)) == 1
+            C.EVP_PKEY_CTX_free(ctx)
+            if not ok:
+                count.append(-1)
+                return
+            n += 1
+        C.EVP_PKEY_free(sk)
+        C.EVP_PKEY_free(pk)
+        count.append(n)
+
+    res = {}
+    for nt in (1, 16):
+        count, stop = [], threading.Event()
+        th = [threading.Thread(target=worker, args=(count, stop)) for _ in range(nt)]
+        t0 = time.perf_counter()
+        for t in th:
+            t.start()
+        time.sleep(seconds)
+        stop.set()
+        for t in th:
+            t.join()
+        if min(count) < 0:
+            return None
+        res[f"threads_{nt}_per_s"] = round(sum(count) / (time.perf_counter() - t0))
+    return res
+
+
+def handshake_leg(eng):
+    """rg_x25519_batch_dev, rg_handshake_init_batch_dev and rg_handshake_resp_batch_dev at 64 Ki and 1 Ki rows
+    (256 distinct valid initiations, tiled: the kernels' timing does not depend on the data), by stream events,
+    medians of seven repetitions with min-max; OpenSSL's X25519 on the CPU beside it, in the same run.  Also
+    written to profiles/handshake_bench.json."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import handshake_cases as hc  # the Python model makes the valid messages
+
+    r = hc.Responder(41, npeers=8, neph=256)
+    base = np.zeros((256, 160), np.uint8)
+    for i in range(256):
+        msg, _ = hc.make_initiation(r.sk_i[i % 8], r.pk_r, r.esk_i[i], hc.tai64n(1_800_000_000, i), i)
+        base[i, :148] = np.frombuffer(msg, np.uint8)
+    peers = hc.peer_rows(r.peers)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    d_own, d_peers, d_table = dev(r.own), dev(peers), dev(aead.peer_table(peers))
+    rng = np.random.default_rng(43)
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    def stats(ts, n, per=1):
+        ts = sorted(ts)
+        med = ts[len(ts) // 2]
+        return {"ms_median": round(med, 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4),
+                "per_s_median": round(n * per / med * 1e3)}
+
+    out = {}
+    for n in (1 << 16, 1 << 10):
+        buf = dev(np.tile(base, (n // 256, 1)).reshape(-1))
+        desc = np.zeros(n, DESC_DTYPE)
+        desc["offset"] = np.arange(n, dtype=np.uint64) * 160
+        desc["len"] = 148
+        d_desc = dev(desc.view(np.uint8).reshape(-1, 16))
+        scal, pts = dev(rng.integers(0, 256, (n, 32), dtype=np.uint8)), dev(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+        xo = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+        st = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        res = torch.zeros((n, 128), dtype=torch.uint8, device="cuda")
+        keep = torch.zeros((n, 128), dtype=torch.uint8, device="cuda")
+        esk = dev(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+        sids = dev(np.arange(n, dtype=np.uint32))
+        resp = torch.zeros((n, 96), dtype=torch.uint8, device="cuda")
+        keys = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+        st2 = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        x = lambda: eng.x25519_dev(scal, pts, xo, st)  # noqa: E731
+        ini = lambda: eng.handshake_init_dev(d_own, d_peers, d_table, d_desc, None, buf, res, st)  # noqa: E731
+        rsp = lambda: eng.handshake_resp_dev(d_peers, res, None, esk, sids, None, None, resp, keys, st2)  # noqa: E731
+        x(), ini()
+        torch.cuda.synchronize()
+        assert (st == aead.PKT_OK).all().item()
+        keep.copy_(res)
+        rsp()
+        torch.cuda.synchronize()
+        assert (st2 == aead.PKT_OK).all().item()
+        t = {"x25519": [], "init": [], "resp": [], "both": []}
+        for _ in range(7):
+            t["x25519"].append(ev_ms(x))
+            t["init"].append(ev_ms(ini))
+            res.copy_(keep)  # the response call consumes its rows: give them back outside the timed window
+            torch.cuda.synchronize()
+            t["resp"].append(ev_ms(rsp))
+            t["both"].append(ev_ms(lambda: (ini(), rsp())))
+        out[f"rows_{n}"] = {"x25519": stats(t["x25519"], n), "init": stats(t["init"], n), "resp": stats(t["resp"], n),
+                            "handshakes": stats(t["both"], n),
+                            "ladders_per_s_in_handshakes": stats(t["both"], n, 5)["per_s_median"]}
+    cpu = _openssl_x25519()
+    out["cpu_openssl_x25519"] = cpu if cpu else "no CPU baseline"
+    out["note"] = ("stream events around one call each, medians of 7 repetitions (one warm-up call before); rows are "
+                   "256 distinct valid initiations over 8 peers, tiled; a handshake = the init call + the response "
+                   "call = 5 X25519 ladders; CPU baseline: EVP_PKEY_derive in a loop per thread, same run")
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "handshake_bench.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "handshake"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
-                      ("replay", replay_leg), ("send", send_leg)):
+                      ("replay", replay_leg), ("send", send_leg), ("handshake", handshake_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
