@@ -243,12 +243,8 @@ int rg_rx_table_build(const uint32_t *receivers, const uint32_t *key_idx, size_t
 
 int64_t rg_rx_table_find(const rg_rx_entry *table, uint32_t cap, uint32_t receiver) {
     if (!table || cap == 0 || (cap & (cap - 1)) != 0) return -1;
-    uint32_t s = rg::rx_slot(receiver, cap);
-    for (uint32_t probe = 0; probe < cap && table[s].key_idx != RG_KEY_SKIP; ++probe) {
-        if (table[s].receiver == receiver) return table[s].key_idx;
-        s = (s + 1) & (cap - 1);
-    }
-    return -1;
+    const uint32_t k = rg::rx_find(table, cap, receiver);
+    return k == RG_KEY_SKIP ? -1 : (int64_t)k;
 }
 
 // Config::get_peer_idx as a table over peer rows (rg_handshake.hip reads it): the receiver table's slot rule

@@ -1,0 +1,273 @@
+// rg_grouped.h -- what a batch pass over packets grouped by a row shares: the device anti-replay commit
+// (rg_replay.hip: row = window, a segmented prefix maximum) and the device send-counter reservation
+// (rg_send.hip: row = session, a segmented count).  Device code and its launchers only.
+//   Grouped          the device view of a batch and its grouped order; also the key of the radix passes
+//   SegPair          the segmented-scan monoid over a value type and an operation
+//   block_prefix     exclusive scan of one SegPair per lane over a workgroup, carry_kernel over the tiles'
+//                    aggregates
+//   GroupLayout      the workspace arrays every such pass has, group_rows their typed pointers and the order
+// How a tile of kGroupTile grouped packets is walked is each file's own: the walk follows the monoid.
+//
+// The grouping is stable, by the passes of an LSD radix sort over the 32-bit key, 8 bits per pass.  KeyOf is
+// a small struct passed by value with `__device__ uint32_t operator()(uint32_t i) const`: the grouping key
+// of packet i (Grouped is one).  One pass:
+//   radix_hist_kernel     digit counts per workgroup of kGroupTile positions
+//   radix_scan_kernel     exclusive prefix sum over the digit-major counts, one workgroup
+//   radix_scatter_kernel  stable scatter behind those offsets
+// group_by_key runs as many passes as the key range needs and returns the grouped order (nullptr for no
+// pass: the array is its own grouping).
+#pragma once
+#include "rg_internal.h"
+
+namespace rg {
+
+constexpr uint32_t kGroupTile = 2048; // packets per workgroup of 256 lanes, in the scans and the radix passes
+constexpr uint32_t kRadixItems = kGroupTile / 256;
+
+// A batch of n packets, each with a row word (rows[i]; RG_KEY_SKIP or >= nrows: no row), and the packet
+// indices grouped by row.  A packet without a row rides along in row 0's group.
+struct Grouped {
+    const uint32_t *rows;  // [n]
+    const uint32_t *order; // [n] packet indices grouped by row, or nullptr: array order
+    uint32_t nrows;
+    uint32_t n;
+    __device__ __forceinline__ bool has_row(uint32_t w) const { return w != RG_KEY_SKIP && w < nrows; }
+    // the grouping key: a packet's row, 0 for a packet without one
+    __device__ __forceinline__ uint32_t key_of(uint32_t i) const {
+        const uint32_t w = rows[i];
+        return has_row(w) ? w : 0u;
+    }
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return key_of(i); }
+    // (the grouped order is a permutation of [0, n); the bound keeps every later access inside the batch's
+    // arrays whatever the workspace holds)
+    __device__ __forceinline__ uint32_t index_at(uint64_t pos) const {
+        return order ? min(order[pos], n - 1) : (uint32_t)pos;
+    }
+    __device__ __forceinline__ uint32_t key_at(uint64_t pos) const { return key_of(index_at(pos)); }
+    // the key ahead of a lane's or wave's first position `base` (a row's head is a change of key)
+    __device__ __forceinline__ uint32_t key_before(uint64_t base) const {
+        return base > 0 && base < n ? key_at(base - 1) : 0u;
+    }
+    // pos holds the last grouped packet of the row `key`: the lane that updates the row
+    __device__ __forceinline__ bool is_tail(uint64_t pos, uint32_t key) const {
+        return pos + 1 == n || key_at(pos + 1) != key;
+    }
+};
+
+// (f, v) of a run of grouped packets: f = the run holds a row's first packet, v = Op over the values since
+// the last such packet.  join is associative; {0, 0} is its identity for the two operations in use.
+template <class V, class Op>
+struct SegPair {
+    using value_type = V;
+    uint32_t f;
+    V v;
+};
+template <class V, class Op>
+__device__ __forceinline__ SegPair<V, Op> join(const SegPair<V, Op> &a, const SegPair<V, Op> &b) {
+    return SegPair<V, Op>{a.f | b.f, b.f ? b.v : Op{}(a.v, b.v)};
+}
+
+// exclusive prefix of one Pair per lane over the workgroup's 256 lanes (returned), and their total
+template <class Pair>
+__device__ __forceinline__ Pair block_prefix(const Pair &mine, Pair &total) {
+    using V = typename Pair::value_type;
+    __shared__ uint32_t s_f[256];
+    __shared__ V s_v[256];
+    const uint32_t t = threadIdx.x;
+    s_f[t] = mine.f;
+    s_v[t] = mine.v;
+    __syncthreads();
+    Pair cur = mine;
+    for (uint32_t off = 1; off < 256; off <<= 1) {
+        const bool has = t >= off;
+        Pair o{0u, V(0)};
+        if (has) o = Pair{s_f[t - off], s_v[t - off]};
+        __syncthreads();
+        if (has) {
+            cur = join(o, cur);
+            s_f[t] = cur.f;
+            s_v[t] = cur.v;
+        }
+        __syncthreads();
+    }
+    total = Pair{s_f[255], s_v[255]};
+    return t ? Pair{s_f[t - 1], s_v[t - 1]} : Pair{0u, V(0)};
+}
+
+// the tiles' aggregates -> what each tile starts from (exclusive), in place; one workgroup
+template <class Pair>
+__global__ __launch_bounds__(256) void carry_kernel(uint32_t *agg_flag, typename Pair::value_type *agg_val,
+                                                    uint32_t nblk) {
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (nblk + 255) / 256, lo = min(t * per, nblk), hi = min(lo + per, nblk);
+    Pair run{0u, 0u};
+    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{agg_flag[j], agg_val[j]});
+    Pair total;
+    Pair ex = block_prefix(run, total);
+    for (uint32_t j = lo; j < hi; ++j) {
+        const Pair cur{agg_flag[j], agg_val[j]};
+        agg_flag[j] = ex.f;
+        agg_val[j] = ex.v;
+        ex = join(ex, cur);
+    }
+}
+
+// 8-bit passes that order keys below nkeys (0: one key, no grouping)
+__host__ __device__ inline uint32_t radix_passes(uint32_t nkeys) {
+    uint32_t p = 0;
+    for (uint32_t top = nkeys ? nkeys - 1 : 0; top; top >>= 8) ++p;
+    return p;
+}
+
+// One pass of a stable LSD radix sort: workgroup b owns positions [b, b + 1) x kGroupTile of src
+// (src == nullptr: the identity).
+template <class KeyOf>
+__global__ __launch_bounds__(256) void radix_hist_kernel(KeyOf key, uint32_t n, uint32_t nblk, const uint32_t *src,
+                                                         uint32_t shift, uint32_t *hist) {
+    __shared__ uint32_t s_h[256];
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile;
+    for (uint32_t k = 0; k < kRadixItems; ++k) {
+        const uint64_t pos = base + k * 256 + threadIdx.x;
+        if (pos < n) atomicAdd(&s_h[(key(src ? src[pos] : (uint32_t)pos) >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(uint64_t)threadIdx.x * nblk + blockIdx.x] = s_h[threadIdx.x];
+}
+
+// exclusive prefix sum over hist[0, total), digit-major: one workgroup, a contiguous run per lane (a
+// template like its neighbours, so that it is emitted beside them in each file that groups)
+template <class KeyOf>
+__global__ __launch_bounds__(1024) void radix_scan_kernel(uint32_t *hist, uint64_t total) {
+    __shared__ uint32_t s_sum[1024];
+    const uint32_t t = threadIdx.x;
+    const uint64_t per = (total + 1023) / 1024, lo = min(t * per, total), hi = min(lo + per, total);
+    uint32_t sum = 0;
+    for (uint64_t j = lo; j < hi; ++j) sum += hist[j];
+    s_sum[t] = sum;
+    __syncthreads();
+    uint32_t cur = sum;
+    for (uint32_t off = 1; off < 1024; off <<= 1) {
+        const uint32_t o = t >= off ? s_sum[t - off] : 0u;
+        __syncthreads();
+        cur += o;
+        s_sum[t] = cur;
+        __syncthreads();
+    }
+    uint32_t run = cur - sum;
+    for (uint64_t j = lo; j < hi; ++j) {
+        const uint32_t c = hist[j];
+        hist[j] = run;
+        run += c;
+    }
+}
+
+// Stable scatter: wave v of the workgroup owns the contiguous quarter v of the tile and walks it 64
+// positions at a time; lanes of one round with the same digit find each other by ballots and take
+// consecutive places behind the digit's running offset.
+template <class KeyOf>
+__global__ __launch_bounds__(256) void radix_scatter_kernel(KeyOf key, uint32_t n, uint32_t nblk, const uint32_t *src,
+                                                            uint32_t *dst, uint32_t shift, const uint32_t *hist) {
+    __shared__ uint32_t s_off[4][256];
+    const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
+    for (uint32_t q = 0; q < 4; ++q) s_off[q][t] = 0;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
+    constexpr uint32_t kRounds = kGroupTile / 256;
+    uint32_t idx[kRounds], dg[kRounds];
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint64_t pos = base + r * 64 + lane;
+        const bool ok = pos < n;
+        idx[r] = ok ? (src ? src[pos] : (uint32_t)pos) : 0u;
+        dg[r] = ok ? (key(idx[r]) >> shift) & 255u : 256u;
+        if (ok) atomicAdd(&s_off[v][dg[r]], 1u);
+    }
+    __syncthreads();
+    { // counts -> first place of (wave, digit): the workgroup's base, then the waves in order
+        uint32_t run = hist[(uint64_t)t * nblk + blockIdx.x];
+        for (uint32_t q = 0; q < 4; ++q) {
+            const uint32_t c = s_off[q][t];
+            s_off[q][t] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const bool ok = dg[r] < 256u;
+        uint64_t same = __ballot(ok);
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            const bool bit = (dg[r] >> b) & 1u;
+            const uint64_t m = __ballot(bit);
+            same &= bit ? m : ~m;
+        }
+        const uint32_t rank = (uint32_t)__popcll(same & ((1ull << lane) - 1));
+        const uint32_t off = ok ? s_off[v][dg[r]] : 0u;
+        __syncthreads();
+        if (ok && rank == 0) s_off[v][dg[r]] = off + (uint32_t)__popcll(same);
+        if (ok) dst[(uint64_t)off + rank] = idx[r];
+        __syncthreads();
+    }
+}
+
+// The grouped order of [0, n) under `key`: `passes` passes ping-ponging between order0 and order1 (order1
+// is touched only from the second pass on), hist = [256][nblk] u32.  Returns where the last pass wrote, or
+// nullptr when passes == 0.
+template <class KeyOf>
+inline const uint32_t *group_by_key(KeyOf key, uint32_t n, uint32_t nblk, uint32_t passes, uint32_t *hist,
+                                    uint32_t *order0, uint32_t *order1, hipStream_t st) {
+    const dim3 tiles(nblk), wg(256);
+    const uint32_t *src = nullptr;
+    for (uint32_t p = 0; p < passes; ++p) {
+        uint32_t *dst = (p & 1) ? order1 : order0;
+        hipLaunchKernelGGL(radix_hist_kernel<KeyOf>, tiles, wg, 0, st, key, n, nblk, src, 8 * p, hist);
+        hipLaunchKernelGGL(radix_scan_kernel<KeyOf>, dim3(1), dim3(1024), 0, st, hist, 256ull * nblk);
+        hipLaunchKernelGGL(radix_scatter_kernel<KeyOf>, tiles, wg, 0, st, key, n, nblk, src, dst, 8 * p,
+                           (const uint32_t *)hist);
+        src = dst;
+    }
+    return src;
+}
+
+// The workspace arrays of a grouped scan, contiguous and in this order in the caller's workspace.
+struct GroupLayout {
+    uint64_t order[2]; // [n] u32 each: packet indices grouped by row (ping-pong of the radix passes)
+    uint64_t hist;     // [256][nblk] u32: digit counts per workgroup
+    uint64_t agg_val;  // [nblk] V and
+    uint64_t agg_flag; // [nblk] u32: per-tile aggregates of the segmented scan
+    uint32_t nblk;     // tiles of kGroupTile packets
+    uint32_t passes;   // 8-bit radix passes over the row index (0: one row, no grouping)
+    void take(WorkspaceCursor &ws, uint64_t n, uint32_t nrows, uint64_t value_size) {
+        nblk = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
+        passes = radix_passes(nrows);
+        order[0] = ws.take(passes > 0 ? n * 4 : 0);
+        order[1] = ws.take(passes > 1 ? n * 4 : 0);
+        hist = ws.take(passes > 0 ? 256ull * nblk * 4 : 0);
+        agg_val = ws.take((uint64_t)nblk * value_size);
+        agg_flag = ws.take((uint64_t)nblk * 4);
+    }
+};
+
+// What the scan kernels of a grouped pass take: the view, the aggregates, the tile count.
+template <class V>
+struct GroupScan : Grouped {
+    V *agg_val;
+    uint32_t *agg_flag;
+    uint32_t nblk;
+};
+// Groups the batch by row on `st` and returns the scan's arguments, out of the workspace at ws.
+template <class V>
+inline GroupScan<V> group_rows(const uint32_t *rows, uint32_t nrows, uint32_t n, uint8_t *ws, const GroupLayout &L,
+                               hipStream_t st) {
+    Grouped g{rows, nullptr, nrows, n};
+    g.order = group_by_key(g, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
+                           reinterpret_cast<uint32_t *>(ws + L.order[0]),
+                           reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
+    return GroupScan<V>{g, reinterpret_cast<V *>(ws + L.agg_val), reinterpret_cast<uint32_t *>(ws + L.agg_flag),
+                        L.nblk};
+}
+
+} // namespace rg

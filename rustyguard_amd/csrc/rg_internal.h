@@ -53,9 +53,9 @@ struct MacArgs {
 };
 hipError_t launch_mac_verify(const MacArgs &a, hipStream_t s);
 
-// Lays a caller's workspace out (replay_layout below, send_layout in rg_send.hip): take(bytes) is the byte
-// offset of the next array from the 16-byte aligned base, each a multiple of 256; total() what was taken,
-// at least 256.
+// Lays a caller's workspace out (replay_layout in rg_replay.hip, send_layout in rg_send.hip): take(bytes) is
+// the byte offset of the next array from the 16-byte aligned base, each a multiple of 256; total() what was
+// taken, at least 256.
 struct WorkspaceCursor {
     uint64_t at = 0;
     uint64_t take(uint64_t bytes) {
@@ -65,53 +65,6 @@ struct WorkspaceCursor {
     }
     uint64_t total() const { return at ? at : 256; }
 };
-
-// Workspace of the device anti-replay calls (rg_replay.hip).  total == 0: the batch is too large.
-constexpr uint32_t kReplayTile = 2048; // packets per workgroup of the scan and radix passes
-struct ReplayLayout {
-    uint64_t rdesc; // [n] rg_pkt_desc: working descriptors of the open (RG_KEY_SKIP = unknown or gated); = 0
-    // commit pass
-    uint64_t hash;     // [hash_cap] u32: earliest RG_PKT_OK packet of each (window, counter)
-    uint64_t order[2]; // [n] u32 each: packet indices grouped by window (ping-pong of the radix passes)
-    uint64_t hist;     // [256][nblk] u32: digit counts per workgroup
-    uint64_t agg_val;  // [nblk] u64 and
-    uint64_t agg_flag; // [nblk] u32: per-workgroup aggregates of the segmented prefix maximum
-    uint64_t lf;       // [n] u64: the running maximum at each window's last packet
-    // resident receive (rdesc at offset 0: include/rg_aead.h documents it to callers)
-    uint64_t ctr;     // [n] u64: header counters
-    uint64_t widx;    // [n] u32: resolved key rows = window rows
-    uint64_t undo;    // [n] u8
-    uint64_t ustatus; // [n] u8: statuses of the re-seal
-    uint64_t udesc;   // [n] rg_pkt_desc: re-seal descriptors
-    uint64_t total;
-    uint64_t hash_cap; // a power of two >= 2 n
-    uint32_t nblk;     // workgroups of kReplayTile packets
-    uint32_t passes;   // 8-bit radix passes over the window index (0: one window, no grouping)
-};
-inline ReplayLayout replay_layout(uint64_t n, uint32_t nwin) {
-    ReplayLayout L{};
-    if (n > 0xFFFFFFFFull) return L; // total = 0
-    WorkspaceCursor ws;
-    L.hash_cap = 64;
-    while (L.hash_cap < 2 * n) L.hash_cap <<= 1;
-    L.nblk = (uint32_t)((n + kReplayTile - 1) / kReplayTile);
-    for (uint32_t top = nwin ? nwin - 1 : 0; top; top >>= 8) ++L.passes;
-    L.rdesc = ws.take(n * sizeof(rg_pkt_desc));
-    L.hash = ws.take(L.hash_cap * 4);
-    L.order[0] = ws.take(L.passes > 0 ? n * 4 : 0);
-    L.order[1] = ws.take(L.passes > 1 ? n * 4 : 0);
-    L.hist = ws.take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
-    L.agg_val = ws.take((uint64_t)L.nblk * 8);
-    L.agg_flag = ws.take((uint64_t)L.nblk * 4);
-    L.lf = ws.take(n * 8);
-    L.ctr = ws.take(n * 8);
-    L.widx = ws.take(n * 4);
-    L.undo = ws.take(n);
-    L.ustatus = ws.take(n);
-    L.udesc = ws.take(n * sizeof(rg_pkt_desc));
-    L.total = ws.total();
-    return L;
-}
 
 // The caller's current HIP device, put back on the way out: every entry point selects its context's
 // device (and a group call each of its contexts' in turn), while the caller -- a torch program, say --
@@ -336,6 +289,28 @@ hipError_t launch_rx_resolve(const rg_pkt_desc *desc, uint32_t n, const uint8_t 
                              hipStream_t s);
 __host__ __device__ __forceinline__ uint32_t rx_slot(uint32_t receiver, uint32_t cap) {
     return cap > 1 ? (receiver * 0x9E3779B1u) >> (32 - __builtin_ctz(cap)) : 0u;
+}
+// the key row of `receiver` in the table (rg_rx_table_build: cap a power of two), or RG_KEY_SKIP
+__host__ __device__ __forceinline__ uint32_t rx_find(const rg_rx_entry *table, uint32_t cap, uint32_t receiver) {
+    uint32_t s = rx_slot(receiver, cap);
+    for (uint32_t probe = 0; probe < cap; ++probe) {
+        const rg_rx_entry e = table[s];
+        if (e.key_idx == RG_KEY_SKIP) break;
+        if (e.receiver == receiver) return e.key_idx;
+        s = (s + 1) & (cap - 1);
+    }
+    return RG_KEY_SKIP;
+}
+// The checks Sessions::decrypt_packet makes ahead of its lookup (rustyguard-core/src/lib.rs:605-650):
+// 16-byte alignment, in the buffer, whole 16-byte segments of at least one, message type 4.  True for such
+// a frame, with its header words (type, receiver, counter low and high) in hdr.
+__device__ __forceinline__ bool rx_frame_header(const rg_pkt_desc &d, const uint8_t *buf, uint64_t buf_len,
+                                                uint4 &hdr) {
+    const uint64_t W = d.len;
+    if ((d.offset & 15u) != 0 || d.offset > buf_len || W > buf_len - d.offset || W < 16 || (W & 15u) != 0)
+        return false;
+    hdr = *reinterpret_cast<const uint4 *>(buf + d.offset);
+    return hdr.x == 4u;
 }
 hipError_t launch_general(GeneralJob *jobs, uint32_t njobs, uint8_t *arena, hipStream_t s);
 // device-resident session batches (rg_sessions.cpp): bind each packet to its key row; gather the

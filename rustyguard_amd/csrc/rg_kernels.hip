@@ -114,24 +114,9 @@ __global__ __launch_bounds__(256) void rx_resolve_kernel(const rg_pkt_desc *desc
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     rg_pkt_desc d = desc[i];
-    const uint64_t W = d.len;
     uint32_t k = 0, found = RG_KEY_SKIP;
-    if ((d.offset & 15u) == 0 && d.offset <= buf_len && W <= buf_len - d.offset && W >= 16 && (W & 15u) == 0) {
-        const uint4 hdr = *reinterpret_cast<const uint4 *>(buf + d.offset);
-        if (hdr.x == 4u) {
-            uint32_t s = rx_slot(hdr.y, cap);
-            for (uint32_t probe = 0; probe < cap; ++probe) {
-                const rg_rx_entry e = table[s];
-                if (e.key_idx == RG_KEY_SKIP) break;
-                if (e.receiver == hdr.y) {
-                    found = e.key_idx;
-                    break;
-                }
-                s = (s + 1) & (cap - 1);
-            }
-            k = found; // RG_KEY_SKIP when unknown: Error::Rejected
-        }
-    }
+    uint4 hdr;
+    if (rx_frame_header(d, buf, buf_len, hdr)) k = found = rx_find(table, cap, hdr.y); // unknown: Error::Rejected
     d.key_idx = k;
     out[i] = d;
     if (key_out) key_out[i] = found;

@@ -16,13 +16,13 @@
 //            accepted packets of block j.
 //
 // Kernels of the commit pass, all on the call's stream:
-//   radix_hist / radix_scan / radix_scatter   (rg_radix.h) stable grouping of the packet indices by window: an LSD radix
+//   radix_hist / radix_scan / radix_scatter   stable grouping of the packet indices by window: an LSD radix
 //            sort over the window index, 8 bits per pass, as many passes as the window count needs (none
 //            for one window: the array is its own grouping)
 //   replay_clear    the (window, counter) table starts empty
 //   replay_reduce   per workgroup of 2048 grouped packets the aggregate of the segmented prefix maximum;
 //            every OK packet enters the (window, counter) table, the smallest packet index winning
-//   replay_carry    one workgroup scans the aggregates
+//   carry           one workgroup scans the aggregates
 //   replay_verdict  every packet's M_p, the three tests, status and undo; the running maximum at each
 //            window's last packet
 //   replay_advance  one lane per window with traffic: the slots the window moved past are cleared, last'
@@ -30,95 +30,76 @@
 // A packet without a window (RG_KEY_SKIP, out of range) or without a verdict to judge (any status but OK /
 // DECRYPT_ERR, RG_PKT_PENDING included) rides along in window 0's group as a neutral element and comes
 // back untouched.
+// Shared with the send-counter reservation (rg_send.hip), in rg_grouped.h: the radix passes, the grouped view
+// of the batch, the segmented pair and its workgroup scan, the carry kernel and the workspace arrays of
+// these.  The walk over a tile (8 consecutive packets a lane, their runs scanned through LDS) is this file's.
 //
 // The entry points' host side is here too (rg_cookie.hip's precedent), on rg_host.h like the host units,
 // none of which names a launcher of this file.  All scratch is the caller's workspace; nothing is
 // allocated, waited for or kept.
 #include "rg_device.h"
 #include "rg_host.h"
-#include "rg_radix.h"
+#include "rg_grouped.h"
 
 namespace rg {
 namespace {
 
-constexpr uint32_t kItems = kReplayTile / 256; // grouped packets per lane, consecutive
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;       // (window, counter) table: free slot (n <= 2^32 - 1)
+// Workspace of the device anti-replay calls (WorkspaceCursor, rg_internal.h).  total == 0: the batch is too
+// large.
+struct ReplayLayout {
+    uint64_t rdesc; // [n] rg_pkt_desc: working descriptors of the open (RG_KEY_SKIP = unknown or gated); = 0
+    // commit pass
+    uint64_t hash; // [hash_cap] u32: earliest RG_PKT_OK packet of each (window, counter)
+    GroupLayout g; // the grouped order and the aggregates (u64) of the segmented prefix maximum
+    uint64_t lf;   // [n] u64: the running maximum at each window's last packet
+    // resident receive (rdesc at offset 0: include/rg_aead.h documents it to callers)
+    uint64_t ctr;     // [n] u64: header counters
+    uint64_t widx;    // [n] u32: resolved key rows = window rows
+    uint64_t undo;    // [n] u8
+    uint64_t ustatus; // [n] u8: statuses of the re-seal
+    uint64_t udesc;   // [n] rg_pkt_desc: re-seal descriptors
+    uint64_t total;
+    uint64_t hash_cap; // a power of two >= 2 n
+};
+ReplayLayout replay_layout(uint64_t n, uint32_t nwin) {
+    ReplayLayout L{};
+    if (n > 0xFFFFFFFFull) return L; // total = 0
+    WorkspaceCursor ws;
+    L.hash_cap = 64;
+    while (L.hash_cap < 2 * n) L.hash_cap <<= 1;
+    L.rdesc = ws.take(n * sizeof(rg_pkt_desc));
+    L.hash = ws.take(L.hash_cap * 4);
+    L.g.take(ws, n, nwin, sizeof(uint64_t));
+    L.lf = ws.take(n * 8);
+    L.ctr = ws.take(n * 8);
+    L.widx = ws.take(n * 4);
+    L.undo = ws.take(n);
+    L.ustatus = ws.take(n);
+    L.udesc = ws.take(n * sizeof(rg_pkt_desc));
+    L.total = ws.total();
+    return L;
+}
+
+constexpr uint32_t kItems = kGroupTile / 256; // grouped packets per lane, consecutive
+constexpr uint32_t kEmpty = 0xFFFFFFFFu;      // (window, counter) table: free slot (n <= 2^32 - 1)
+
+// ------------------------------------------- segmented prefix maximum
+// v = the largest OK counter since the window's first packet (0 when none: every window's last is >= 0)
+struct MaxOp {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
+};
+using Pair = SegPair<uint64_t, MaxOp>;
 
 struct ReplayArgs {
     rg_antireplay *windows;
-    const uint32_t *win_idx;  // [n]
     const uint64_t *counters; // [n]
     uint8_t *status;          // [n]
     uint8_t *undo;            // [n] or nullptr
-    const uint32_t *order;    // [n] packet indices grouped by window, or nullptr: array order
     uint32_t *hash;
     uint64_t hash_mask;
-    uint64_t *agg_val;
-    uint32_t *agg_flag;
     uint64_t *lf;
-    uint32_t nwin;
-    uint32_t n;
-    uint32_t nblk;
+    GroupScan<uint64_t> g; // g.rows = the packets' window rows
 };
-
-// (the grouped order is a permutation of [0, n); the bound keeps every later access inside the batch's
-// arrays whatever the workspace holds)
-__device__ __forceinline__ uint32_t index_at(const ReplayArgs &a, uint64_t pos) {
-    return a.order ? min(a.order[pos], a.n - 1) : (uint32_t)pos;
-}
-__device__ __forceinline__ bool has_window(const ReplayArgs &a, uint32_t w) { return w != RG_KEY_SKIP && w < a.nwin; }
-// the grouping key: a packet's window, 0 for a packet without one
-__device__ __forceinline__ uint32_t group_of(const ReplayArgs &a, uint32_t i) {
-    const uint32_t w = a.win_idx[i];
-    return has_window(a, w) ? w : 0u;
-}
-
-// ------------------------------------------------------- grouping by window
-// the key of the shared radix passes (rg_radix.h)
-struct WindowKey {
-    const uint32_t *win_idx;
-    uint32_t nwin;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
-        const uint32_t w = win_idx[i];
-        return w != RG_KEY_SKIP && w < nwin ? w : 0u;
-    }
-};
-
-// ------------------------------------------- segmented prefix maximum
-// (f, v): f = the run holds a window's first packet, v = the largest OK counter since the last such
-// packet (0 when none: every window's last is >= 0).  join is associative.
-struct Pair {
-    uint32_t f;
-    uint64_t v;
-};
-__device__ __forceinline__ Pair join(const Pair &a, const Pair &b) {
-    return Pair{a.f | b.f, b.f ? b.v : (a.v > b.v ? a.v : b.v)};
-}
-
-// exclusive prefix of one Pair per lane over the workgroup's 256 lanes (returned), and their total
-__device__ __forceinline__ Pair block_prefix(const Pair &mine, Pair &total) {
-    __shared__ uint32_t s_f[256];
-    __shared__ uint64_t s_v[256];
-    const uint32_t t = threadIdx.x;
-    s_f[t] = mine.f;
-    s_v[t] = mine.v;
-    __syncthreads();
-    Pair cur = mine;
-    for (uint32_t off = 1; off < 256; off <<= 1) {
-        const bool has = t >= off;
-        Pair o{0u, 0ull};
-        if (has) o = Pair{s_f[t - off], s_v[t - off]};
-        __syncthreads();
-        if (has) {
-            cur = join(o, cur);
-            s_f[t] = cur.f;
-            s_v[t] = cur.v;
-        }
-        __syncthreads();
-    }
-    total = Pair{s_f[255], s_v[255]};
-    return t ? Pair{s_f[t - 1], s_v[t - 1]} : Pair{0u, 0ull};
-}
 
 // ------------------------------------------- (window, counter) -> earliest OK packet
 __device__ __forceinline__ uint64_t hash_slot(uint32_t w, uint64_t c, uint64_t mask) {
@@ -138,7 +119,7 @@ __device__ __forceinline__ void hash_insert(const ReplayArgs &a, uint32_t i, uin
     for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
         const uint32_t e = atomicCAS(&a.hash[s], kEmpty, i);
         if (e == kEmpty) return;
-        if (a.win_idx[e] == w && a.counters[e] == c) {
+        if (a.g.rows[e] == w && a.counters[e] == c) {
             atomicMin(&a.hash[s], i);
             return;
         }
@@ -148,7 +129,7 @@ __device__ __forceinline__ uint32_t hash_find(const ReplayArgs &a, uint32_t w, u
     for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
         const uint32_t e = a.hash[s];
         if (e == kEmpty) return kEmpty;
-        if (a.win_idx[e] == w && a.counters[e] == c) return e;
+        if (a.g.rows[e] == w && a.counters[e] == c) return e;
     }
 }
 
@@ -166,9 +147,9 @@ struct Item {
 };
 __device__ __forceinline__ Item load_item(const ReplayArgs &a, uint64_t pos, uint32_t prev_key) {
     Item it{};
-    it.i = index_at(a, pos);
-    it.w = a.win_idx[it.i];
-    const bool win = has_window(a, it.w);
+    it.i = a.g.index_at(pos);
+    it.w = a.g.rows[it.i];
+    const bool win = a.g.has_row(it.w);
     it.key = win ? it.w : 0u;
     it.st = win ? a.status[it.i] : 0xFFu;
     it.ctr = win && it.st <= RG_PKT_DECRYPT_ERR ? a.counters[it.i] : 0ull;
@@ -180,12 +161,12 @@ __device__ __forceinline__ Pair pair_of(const Item &it) {
 }
 
 __global__ __launch_bounds__(256) void replay_reduce_kernel(ReplayArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + threadIdx.x * kItems;
-    uint32_t prev = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
+    uint32_t prev = a.g.key_before(base);
     Pair run{0u, 0ull};
     for (uint32_t k = 0; k < kItems; ++k) {
         const uint64_t pos = base + k;
-        if (pos >= a.n) break;
+        if (pos >= a.g.n) break;
         const Item it = load_item(a, pos, prev);
         prev = it.key;
         if (it.st == RG_PKT_OK) hash_insert(a, it.i, it.w, it.ctr);
@@ -194,36 +175,20 @@ __global__ __launch_bounds__(256) void replay_reduce_kernel(ReplayArgs a) {
     Pair total;
     (void)block_prefix(run, total);
     if (threadIdx.x == 0) {
-        a.agg_flag[blockIdx.x] = total.f;
-        a.agg_val[blockIdx.x] = total.v;
-    }
-}
-
-// aggregates -> what each workgroup starts from (exclusive), in place; one workgroup
-__global__ __launch_bounds__(256) void replay_carry_kernel(ReplayArgs a) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (a.nblk + 255) / 256, lo = min(t * per, a.nblk), hi = min(lo + per, a.nblk);
-    Pair run{0u, 0ull};
-    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{a.agg_flag[j], a.agg_val[j]});
-    Pair total;
-    Pair ex = block_prefix(run, total);
-    for (uint32_t j = lo; j < hi; ++j) {
-        const Pair cur{a.agg_flag[j], a.agg_val[j]};
-        a.agg_flag[j] = ex.f;
-        a.agg_val[j] = ex.v;
-        ex = join(ex, cur);
+        a.g.agg_flag[blockIdx.x] = total.f;
+        a.g.agg_val[blockIdx.x] = total.v;
     }
 }
 
 __global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kReplayTile + threadIdx.x * kItems;
-    uint32_t prev = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
+    uint32_t prev = a.g.key_before(base);
     Item items[kItems];
     Pair run{0u, 0ull};
 #pragma unroll
     for (uint32_t k = 0; k < kItems; ++k) {
         const uint64_t pos = base + k;
-        if (pos < a.n) {
+        if (pos < a.g.n) {
             items[k] = load_item(a, pos, prev);
             prev = items[k].key;
             run = join(run, pair_of(items[k]));
@@ -234,11 +199,11 @@ __global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
     }
     Pair total;
     const Pair mine = block_prefix(run, total);
-    Pair ex = join(Pair{a.agg_flag[blockIdx.x], a.agg_val[blockIdx.x]}, mine);
+    Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, mine);
 #pragma unroll
     for (uint32_t k = 0; k < kItems; ++k) {
         const uint64_t pos = base + k;
-        if (pos >= a.n) break;
+        if (pos >= a.g.n) break;
         const Item &it = items[k];
         const uint64_t before = it.head ? 0ull : ex.v; // largest OK counter of the window ahead of this packet
         ex = join(ex, pair_of(it));
@@ -262,8 +227,7 @@ __global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
         }
         if (a.undo) a.undo[it.i] = undo;
         // the window's last packet of the batch hands the running maximum to replay_advance
-        const bool tail = pos + 1 == a.n || group_of(a, index_at(a, pos + 1)) != it.key;
-        if (tail) a.lf[pos] = ex.v;
+        if (a.g.is_tail(pos, it.key)) a.lf[pos] = ex.v;
     }
 }
 
@@ -272,10 +236,10 @@ __global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
 // blocks leaves no block j <= L0 / 64 in reach, so every slot is cleared.
 __global__ __launch_bounds__(256) void replay_advance_kernel(ReplayArgs a) {
     const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (pos >= a.n) return;
-    const uint32_t key = group_of(a, index_at(a, pos));
-    if (pos + 1 != a.n && group_of(a, index_at(a, pos + 1)) == key) return;
-    if (key >= a.nwin) return; // no window at all
+    if (pos >= a.g.n) return;
+    const uint32_t key = a.g.key_at(pos);
+    if (!a.g.is_tail(pos, key)) return;
+    if (key >= a.g.nrows) return; // no window at all
     rg_antireplay &win = a.windows[key];
     const uint64_t L0 = win.last, Lf = a.lf[pos];
     if (Lf <= L0) return; // nothing accepted above last: no slot changes hands
@@ -289,9 +253,9 @@ __global__ __launch_bounds__(256) void replay_advance_kernel(ReplayArgs a) {
 
 __global__ __launch_bounds__(256) void replay_mark_kernel(ReplayArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n) return;
-    const uint32_t w = a.win_idx[i];
-    if (!has_window(a, w) || a.status[i] != RG_PKT_OK) return;
+    if (i >= a.g.n) return;
+    const uint32_t w = a.g.rows[i];
+    if (!a.g.has_row(w) || a.status[i] != RG_PKT_OK) return;
     rg_antireplay &win = a.windows[w];
     const uint64_t c = a.counters[i];
     if ((win.last >> 6) - (c >> 6) < 32) // else the window has moved past its block since
@@ -314,26 +278,19 @@ hipError_t launch_commit(rg_antireplay *windows, uint32_t nwin, const uint32_t *
     }
     ReplayArgs a{};
     a.windows = windows;
-    a.win_idx = win_idx;
     a.counters = counters;
     a.status = status;
     a.undo = undo;
     a.hash = reinterpret_cast<uint32_t *>(ws + L.hash);
     a.hash_mask = L.hash_cap - 1;
-    a.agg_val = reinterpret_cast<uint64_t *>(ws + L.agg_val);
-    a.agg_flag = reinterpret_cast<uint32_t *>(ws + L.agg_flag);
     a.lf = reinterpret_cast<uint64_t *>(ws + L.lf);
-    a.nwin = nwin;
-    a.n = n;
-    a.nblk = L.nblk;
-    const dim3 tiles(L.nblk);
-    a.order = group_by_key(WindowKey{win_idx, nwin}, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
-                           reinterpret_cast<uint32_t *>(ws + L.order[0]), reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
+    a.g = group_rows<uint64_t>(win_idx, nwin, n, ws, L.g, st);
+    const dim3 tiles(L.g.nblk);
     const uint64_t quads = L.hash_cap / 4;
     hipLaunchKernelGGL(replay_clear_kernel, dim3((uint32_t)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048)), wg, 0, st,
                        reinterpret_cast<uint4 *>(a.hash), quads);
     hipLaunchKernelGGL(replay_reduce_kernel, tiles, wg, 0, st, a);
-    hipLaunchKernelGGL(replay_carry_kernel, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(carry_kernel<Pair>, dim3(1), wg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
     hipLaunchKernelGGL(replay_verdict_kernel, tiles, wg, 0, st, a);
     hipLaunchKernelGGL(replay_advance_kernel, per_packet, wg, 0, st, a);
     hipLaunchKernelGGL(replay_mark_kernel, per_packet, wg, 0, st, a);
@@ -359,7 +316,8 @@ struct ResidentArgs {
     uint64_t *counters_out; // undo pass, or nullptr
 };
 
-// rx_resolve_kernel (rg_kernels.hip) with the would_accept pre-check of prim.rs:414-420: a frame whose
+// rx_resolve_kernel (rg_kernels.hip; the frame check and the lookup are rg_internal.h's, shared with it)
+// with the would_accept pre-check of prim.rs:414-420: a frame whose
 // session is known and whose header counter the window, as it stands before the batch, would not accept
 // goes to the open kernels as RG_KEY_SKIP -- RG_PKT_REJECTED, no AEAD work, frame untouched.  Exact: last
 // only grows, and a seen bit leaves the window only when its counter has become too old.
@@ -367,31 +325,17 @@ __global__ __launch_bounds__(256) void resident_gate_kernel(ResidentArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
     rg_pkt_desc d = a.desc[i];
-    const uint64_t W = d.len;
     uint32_t k = 0, found = RG_KEY_SKIP;
     uint64_t ctr = 0;
-    if ((d.offset & 15u) == 0 && d.offset <= a.buf_len && W <= a.buf_len - d.offset && W >= 16 && (W & 15u) == 0) {
-        const uint4 hdr = *reinterpret_cast<const uint4 *>(a.buf + d.offset);
-        if (hdr.x == 4u) {
-            ctr = ((uint64_t)hdr.w << 32) | hdr.z;
-            uint32_t s = rx_slot(hdr.y, a.cap);
-            for (uint32_t probe = 0; probe < a.cap; ++probe) {
-                const rg_rx_entry e = a.table[s];
-                if (e.key_idx == RG_KEY_SKIP) break;
-                if (e.receiver == hdr.y) {
-                    found = e.key_idx;
-                    break;
-                }
-                s = (s + 1) & (a.cap - 1);
-            }
-            k = found;
-            if (found != RG_KEY_SKIP && found < a.nkeys) {
-                const rg_antireplay &win = a.windows[found];
-                const uint64_t last = win.last;
-                if (ctr <= last &&
-                    (last - ctr >= RG_REPLAY_WINDOW || ((win.bitmap[(ctr >> 6) & 31] >> (ctr & 63)) & 1ull)))
-                    k = RG_KEY_SKIP;
-            }
+    uint4 hdr;
+    if (rx_frame_header(d, a.buf, a.buf_len, hdr)) {
+        ctr = ((uint64_t)hdr.w << 32) | hdr.z;
+        k = found = rx_find(a.table, a.cap, hdr.y);
+        if (found != RG_KEY_SKIP && found < a.nkeys) {
+            const rg_antireplay &win = a.windows[found];
+            const uint64_t last = win.last;
+            if (ctr <= last && (last - ctr >= RG_REPLAY_WINDOW || ((win.bitmap[(ctr >> 6) & 31] >> (ctr & 63)) & 1ull)))
+                k = RG_KEY_SKIP;
         }
     }
     d.key_idx = k;

@@ -13,58 +13,50 @@
 // r is a stable segmented exclusive count of eligibility flags over the packets grouped by row.
 //
 // Kernels, all on the call's stream:
-//   radix_hist / radix_scan / radix_scatter   (rg_radix.h) stable grouping of the packet indices by row; none
-//            for one row: the array is its own grouping
+//   radix_hist / radix_scan / radix_scatter   stable grouping of the packet indices by row; none for one row:
+//            the array is its own grouping
 //   send_reduce    per workgroup of 2048 grouped packets the aggregate of the segmented count: each wave
 //            walks its quarter 64 packets a round (ballots of eligibility and of row heads, popcounts), the
 //            four waves meet in LDS
-//   send_carry     one workgroup scans the aggregates
+//   carry          one workgroup scans the aggregates
 //   send_verdict   every packet's rank, then status, counter, rekey flag and working descriptor; |E| at each
 //            row's last packet
 //   send_update    one lane per row with traffic: counter', sent'
 //   send_overlay   (resident send) the verdicts of packets without a counter over the seal's statuses
 // A packet without a row (RG_KEY_SKIP, out of range) rides along in row 0's group, not eligible.
 // Plain vector stores only; no atomics on global memory.
+// Shared with the anti-replay commit (rg_replay.hip), in rg_grouped.h: the radix passes, the grouped view of
+// the batch, the segmented pair, the carry kernel and the workspace arrays of these.  The walk over a tile
+// (ballots and popcounts, since the value is a count of flags) is this file's.
 //
 // The entry points' host side is here too (rg_replay.hip's precedent), on rg_host.h like the host units.
 // All scratch is the caller's workspace; nothing is allocated, waited for or kept.
 #include "rg_device.h"
 #include "rg_host.h"
-#include "rg_radix.h"
+#include "rg_grouped.h"
 
 namespace rg {
 namespace {
 
 constexpr uint64_t kRejectAfterTimeNs = 180ull * 1000000000ull; // REJECT_AFTER_TIME, lib.rs:204-209
-constexpr uint32_t kRounds = kRadixTile / 256;                  // rounds of 64 packets per wave
+constexpr uint32_t kRounds = kGroupTile / 256;                  // rounds of 64 packets per wave
 
 // Workspace of the device send calls (WorkspaceCursor, rg_internal.h).  total == 0: the batch is too large.
 // Every term is non-decreasing in n and in nkeys.
 struct SendLayout {
-    uint64_t wdesc;    // [n] rg_pkt_desc: working descriptors (RG_KEY_SKIP = took no counter); = 0
-    uint64_t order[2]; // [n] u32 each: packet indices grouped by row (ping-pong of the radix passes)
-    uint64_t hist;     // [256][nblk] u32
-    uint64_t agg_val;  // [nblk] u32 and
-    uint64_t agg_flag; // [nblk] u32: per-workgroup aggregates of the segmented count
-    uint64_t tot;      // [n] u32: |E| at each row's last grouped packet
-    uint64_t verdict;  // [n] u8: the reserve's statuses (resident send)
-    uint64_t ctr;      // [n] u64: reserved counters when the caller passes no counters_out (resident send)
+    uint64_t wdesc;   // [n] rg_pkt_desc: working descriptors (RG_KEY_SKIP = took no counter); = 0
+    GroupLayout g;    // the grouped order and the aggregates (u32) of the segmented count
+    uint64_t tot;     // [n] u32: |E| at each row's last grouped packet
+    uint64_t verdict; // [n] u8: the reserve's statuses (resident send)
+    uint64_t ctr;     // [n] u64: reserved counters when the caller passes no counters_out (resident send)
     uint64_t total;
-    uint32_t nblk;
-    uint32_t passes;
 };
 SendLayout send_layout(uint64_t n, uint32_t nkeys) {
     SendLayout L{};
     if (n > 0xFFFFFFFFull) return L;
     WorkspaceCursor ws;
-    L.nblk = (uint32_t)((n + kRadixTile - 1) / kRadixTile);
-    L.passes = radix_passes(nkeys);
     L.wdesc = ws.take(n * sizeof(rg_pkt_desc));
-    L.order[0] = ws.take(L.passes > 0 ? n * 4 : 0);
-    L.order[1] = ws.take(L.passes > 1 ? n * 4 : 0);
-    L.hist = ws.take(L.passes > 0 ? 256ull * L.nblk * 4 : 0);
-    L.agg_val = ws.take((uint64_t)L.nblk * 4);
-    L.agg_flag = ws.take((uint64_t)L.nblk * 4);
+    L.g.take(ws, n, nkeys, sizeof(uint32_t));
     L.tot = ws.take(n * 4);
     L.verdict = ws.take(n);
     L.ctr = ws.take(n * 8);
@@ -74,50 +66,25 @@ SendLayout send_layout(uint64_t n, uint32_t nkeys) {
 
 struct SendArgs {
     rg_send_state *state;
-    const uint32_t *slots;   // [n]
     const rg_pkt_desc *desc; // [n]
     const uint64_t *now_ns;  // one u64, or nullptr: no time rule
     uint8_t *status;         // [n]
     uint64_t *counters_out;  // [n]
     uint8_t *rekey_out;      // [n] or nullptr
     rg_pkt_desc *wdesc;      // [n]
-    const uint32_t *order;   // [n] packet indices grouped by row, or nullptr: array order
-    uint32_t *agg_val;
-    uint32_t *agg_flag;
     uint32_t *tot;
-    uint32_t nkeys;
-    uint32_t n;
-    uint32_t nblk;
+    GroupScan<uint32_t> g;   // g.rows = the packets' slot words
 };
 
-struct RowKey { // the key of the shared radix passes: a packet's row, 0 for a packet without one
-    const uint32_t *slots;
-    uint32_t nkeys;
-    __device__ __forceinline__ uint32_t operator()(uint32_t i) const {
-        const uint32_t w = slots[i];
-        return w != RG_KEY_SKIP && w < nkeys ? w : 0u;
-    }
-};
-
-// (the grouped order is a permutation of [0, n); the bound keeps every later access inside the batch's
-// arrays whatever the workspace holds)
-__device__ __forceinline__ uint32_t index_at(const SendArgs &a, uint64_t pos) {
-    return a.order ? min(a.order[pos], a.n - 1) : (uint32_t)pos;
-}
-__device__ __forceinline__ bool has_row(const SendArgs &a, uint32_t w) { return w != RG_KEY_SKIP && w < a.nkeys; }
-__device__ __forceinline__ uint32_t group_of(const SendArgs &a, uint32_t i) {
-    const uint32_t w = a.slots[i];
-    return has_row(a, w) ? w : 0u;
-}
 __device__ __forceinline__ bool expired(const SendArgs &a, uint32_t w, bool timed, uint64_t now) {
     return timed && a.state[w].started_ns + kRejectAfterTimeNs < now; // u64 wrapping add, as the host
 }
 
-// (f, v): f = the run holds a row's first packet, v = eligible packets since the last such packet.
-struct Pair {
-    uint32_t f, v;
+// segmented count: v = eligible packets since the row's first packet
+struct AddOp {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
 };
-__device__ __forceinline__ Pair join(const Pair &a, const Pair &b) { return Pair{a.f | b.f, b.f ? b.v : a.v + b.v}; }
+using Pair = SegPair<uint32_t, AddOp>;
 
 // One grouped packet as the scan sees it.  (f, v) is the packet's exclusive prefix inside its wave's quarter
 // of the tile: f = a row began at or before it there, v = eligible packets of its row ahead of it there.
@@ -133,28 +100,28 @@ struct Item {
 __device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kRounds], Pair &total) {
     __shared__ uint32_t s_f[4], s_v[4];
     const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
-    const uint64_t base = (uint64_t)blockIdx.x * kRadixTile + v * (kRadixTile / 4);
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
     const bool timed = a.now_ns != nullptr;
     const uint64_t now = timed ? *a.now_ns : 0ull;
     const uint64_t below = (1ull << lane) - 1, upto = (2ull << lane) - 1;
     // the key ahead of this wave's first position (a row's head is a change of key)
-    uint32_t last_key = base > 0 && base < a.n ? group_of(a, index_at(a, base - 1)) : 0u;
+    uint32_t last_key = a.g.key_before(base);
     Pair run{0u, 0u};
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; ++r) {
         const uint64_t pos = base + r * 64 + lane;
         Item it{0xFFFFFFFFu, RG_KEY_SKIP, 0u, 0u, 0u, false};
         bool head = false;
-        if (pos < a.n) {
-            it.i = index_at(a, pos);
-            it.w = a.slots[it.i];
-            const bool row = has_row(a, it.w);
+        if (pos < a.g.n) {
+            it.i = a.g.index_at(pos);
+            it.w = a.g.rows[it.i];
+            const bool row = a.g.has_row(it.w);
             it.key = row ? it.w : 0u;
             it.elig = row && (a.desc[it.i].len & 15u) == 0 && !expired(a, it.w, timed, now);
         }
         const uint32_t up = __shfl_up(it.key, 1);
         const uint32_t prev = lane ? up : last_key;
-        if (pos < a.n) head = pos == 0 || it.key != prev;
+        if (pos < a.g.n) head = pos == 0 || it.key != prev;
         const uint64_t H = __ballot(head), E = __ballot(it.elig);
         const uint64_t hm = H & upto;
         if (hm) { // the packet's row began in this round
@@ -193,40 +160,8 @@ __global__ __launch_bounds__(256) void send_reduce_kernel(SendArgs a) {
     Pair total;
     (void)tile_scan(a, items, total);
     if (threadIdx.x == 0) {
-        a.agg_flag[blockIdx.x] = total.f;
-        a.agg_val[blockIdx.x] = total.v;
-    }
-}
-
-// aggregates -> what each workgroup starts from (exclusive), in place; one workgroup
-__global__ __launch_bounds__(256) void send_carry_kernel(SendArgs a) {
-    __shared__ uint32_t s_f[256], s_v[256];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (a.nblk + 255) / 256, lo = min(t * per, a.nblk), hi = min(lo + per, a.nblk);
-    Pair run{0u, 0u};
-    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{a.agg_flag[j], a.agg_val[j]});
-    s_f[t] = run.f;
-    s_v[t] = run.v;
-    __syncthreads();
-    Pair cur = run;
-    for (uint32_t off = 1; off < 256; off <<= 1) {
-        const bool has = t >= off;
-        Pair o{0u, 0u};
-        if (has) o = Pair{s_f[t - off], s_v[t - off]};
-        __syncthreads();
-        if (has) {
-            cur = join(o, cur);
-            s_f[t] = cur.f;
-            s_v[t] = cur.v;
-        }
-        __syncthreads();
-    }
-    Pair ex = t ? Pair{s_f[t - 1], s_v[t - 1]} : Pair{0u, 0u};
-    for (uint32_t j = lo; j < hi; ++j) {
-        const Pair c{a.agg_flag[j], a.agg_val[j]};
-        a.agg_flag[j] = ex.f;
-        a.agg_val[j] = ex.v;
-        ex = join(ex, c);
+        a.g.agg_flag[blockIdx.x] = total.f;
+        a.g.agg_val[blockIdx.x] = total.v;
     }
 }
 
@@ -234,20 +169,20 @@ __global__ __launch_bounds__(256) void send_verdict_kernel(SendArgs a) {
     Item items[kRounds];
     Pair total;
     const Pair wave_ex = tile_scan(a, items, total);
-    const Pair ex = join(Pair{a.agg_flag[blockIdx.x], a.agg_val[blockIdx.x]}, wave_ex);
+    const Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, wave_ex);
     const uint32_t v = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t base = (uint64_t)blockIdx.x * kRadixTile + v * (kRadixTile / 4);
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; ++r) {
         const Item &it = items[r];
         const uint64_t pos = base + r * 64 + lane;
-        if (pos >= a.n) continue;
+        if (pos >= a.g.n) continue;
         const uint64_t rank = it.f ? (uint64_t)it.v : (uint64_t)ex.v + it.v; // eligible packets of the row ahead
         rg_pkt_desc d = a.desc[it.i];
         d.key_idx = RG_KEY_SKIP;
         uint64_t ctr = 0;
         uint8_t st = RG_PKT_REJECTED, rekey = 0;
-        if (has_row(a, it.w)) {
+        if (a.g.has_row(it.w)) {
             if ((d.len & 15u) != 0) st = RG_PKT_INVALID; // takes no counter
             else if (it.elig) {                          // else the row has expired
                 const uint64_t C0 = a.state[it.w].counter;
@@ -265,18 +200,17 @@ __global__ __launch_bounds__(256) void send_verdict_kernel(SendArgs a) {
         if (a.rekey_out) a.rekey_out[it.i] = rekey;
         a.wdesc[it.i] = d;
         // the row's last packet of the batch hands |E| to send_update
-        const bool tail = pos + 1 == a.n || group_of(a, index_at(a, pos + 1)) != it.key;
-        if (tail) a.tot[pos] = (uint32_t)rank + (it.elig ? 1u : 0u);
+        if (a.g.is_tail(pos, it.key)) a.tot[pos] = (uint32_t)rank + (it.elig ? 1u : 0u);
     }
 }
 
 // One lane per row with traffic (the lane of its last grouped packet).
 __global__ __launch_bounds__(256) void send_update_kernel(SendArgs a) {
     const uint64_t pos = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (pos >= a.n) return;
-    const uint32_t key = group_of(a, index_at(a, pos));
-    if (pos + 1 != a.n && group_of(a, index_at(a, pos + 1)) == key) return;
-    if (key >= a.nkeys) return;
+    if (pos >= a.g.n) return;
+    const uint32_t key = a.g.key_at(pos);
+    if (!a.g.is_tail(pos, key)) return;
+    if (key >= a.g.nrows) return;
     rg_send_state &row = a.state[key];
     const uint64_t C0 = row.counter, E = a.tot[pos];
     const uint64_t room = C0 < RG_REJECT_AFTER_MESSAGES ? RG_REJECT_AFTER_MESSAGES - C0 : 0ull;
@@ -289,7 +223,7 @@ __global__ __launch_bounds__(256) void send_update_kernel(SendArgs a) {
 // no rows at all (nkeys == 0): every packet is rejected
 __global__ __launch_bounds__(256) void send_none_kernel(SendArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n) return;
+    if (i >= a.g.n) return;
     rg_pkt_desc d = a.desc[i];
     d.key_idx = RG_KEY_SKIP;
     a.status[i] = RG_PKT_REJECTED;
@@ -311,28 +245,22 @@ hipError_t launch_reserve(rg_send_state *state, uint32_t nkeys, const uint32_t *
                           uint8_t *rekey_out, uint8_t *ws, const SendLayout &L, hipStream_t st) {
     SendArgs a{};
     a.state = state;
-    a.slots = slots;
     a.desc = desc;
     a.now_ns = now_ns;
     a.status = status;
     a.counters_out = counters_out;
     a.rekey_out = rekey_out;
     a.wdesc = reinterpret_cast<rg_pkt_desc *>(ws + L.wdesc);
-    a.agg_val = reinterpret_cast<uint32_t *>(ws + L.agg_val);
-    a.agg_flag = reinterpret_cast<uint32_t *>(ws + L.agg_flag);
     a.tot = reinterpret_cast<uint32_t *>(ws + L.tot);
-    a.nkeys = nkeys;
-    a.n = n;
-    a.nblk = L.nblk;
-    const dim3 per_packet((n + 255) / 256), tiles(L.nblk), wg(256);
+    const dim3 per_packet((n + 255) / 256), tiles(L.g.nblk), wg(256);
     if (nkeys == 0) {
+        a.g.n = n;
         hipLaunchKernelGGL(send_none_kernel, per_packet, wg, 0, st, a);
         return hipGetLastError();
     }
-    a.order = group_by_key(RowKey{slots, nkeys}, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
-                           reinterpret_cast<uint32_t *>(ws + L.order[0]), reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
+    a.g = group_rows<uint32_t>(slots, nkeys, n, ws, L.g, st);
     hipLaunchKernelGGL(send_reduce_kernel, tiles, wg, 0, st, a);
-    hipLaunchKernelGGL(send_carry_kernel, dim3(1), wg, 0, st, a);
+    hipLaunchKernelGGL(carry_kernel<Pair>, dim3(1), wg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
     hipLaunchKernelGGL(send_verdict_kernel, tiles, wg, 0, st, a);
     hipLaunchKernelGGL(send_update_kernel, per_packet, wg, 0, st, a);
     return hipGetLastError();

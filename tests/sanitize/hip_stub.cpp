@@ -291,18 +291,7 @@ hipError_t launch_rx_resolve(const rg_pkt_desc *desc, uint32_t n, const uint8_t 
         if ((d.offset & 15u) == 0 && d.offset <= buf_len && W <= buf_len - d.offset && W >= 16 && (W & 15u) == 0) {
             uint32_t hdr[2];
             memcpy(hdr, buf + d.offset, 8);
-            if (hdr[0] == 4u) {
-                uint32_t s = rx_slot(hdr[1], cap);
-                for (uint32_t probe = 0; probe < cap; ++probe) {
-                    if (table[s].key_idx == RG_KEY_SKIP) break;
-                    if (table[s].receiver == hdr[1]) {
-                        found = table[s].key_idx;
-                        break;
-                    }
-                    s = (s + 1) & (cap - 1);
-                }
-                k = found;
-            }
+            if (hdr[0] == 4u) k = found = rx_find(table, cap, hdr[1]);
         }
         d.key_idx = k;
         out[i] = d;

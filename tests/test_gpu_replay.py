@@ -94,6 +94,12 @@ def test_interleaved_windows(engine, seed, length):
     assert np.array_equal(st[untouched], sts[untouched])
 
 
+def test_interleaved_windows_beyond_one_tile(engine):
+    """Three windows over 4100 packets: three scan tiles, and the third window's first grouped packet lies
+    inside the second, so its verdicts depend on the head flag that the carry hands from tile to tile."""
+    check(engine, rc.interleaved(0, 4100))
+
+
 def test_many_windows_few_packets(engine):
     check(engine, rc.many_windows())
 

@@ -40,6 +40,10 @@ def test_workspace_size():
         sizes = [size(n, nwin) for nwin in (0, 1, 2, 3, 255, 256, 257, 65536, 65537, 1 << 24, (1 << 24) + 1, 0xFFFFFFFF)]
         assert all(a <= b for a, b in zip(sizes, sizes[1:])), (n, sizes)
     assert size(1 << 32, 1) == 0  # n > 2^32 - 1 is refused by the calls
+    # the layout's bytes, pinned: (n, nwin) with no, one, two and three radix passes
+    pinned = {(0, 0): 256, (1, 1): 2560, (2049, 2): 156160, (2049, 257): 164608, (65536, 256): 4358656,
+              (1 << 20, 65537): 73930752, ((1 << 32) - 1, 257): 302820360192}
+    assert {k: size(*k) for k in pinned} == pinned
 
 
 def closed_form(windows, win_idx, counters, status):

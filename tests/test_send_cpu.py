@@ -64,6 +64,10 @@ def test_workspace_size():
         sizes = [size(n, nkeys) for nkeys in (0, 1, 2, 3, 255, 256, 257, 65536, 65537, 1 << 24, (1 << 24) + 1, 0xFFFFFFFF)]
         assert all(a <= b for a, b in zip(sizes, sizes[1:])), (n, sizes)
     assert size(4097, 3) >= 4097 * 16  # the working descriptors alone
+    # the layout's bytes, pinned: (n, nkeys) with no, one, two and three radix passes
+    pinned = {(0, 0): 256, (1, 1): 1536, (2049, 2): 71424, (2049, 257): 79872, (65536, 256): 2195968,
+              (1 << 20, 65537): 39325696, ((1 << 32) - 1, 257): 161078050816}
+    assert {k: size(*k) for k in pinned} == pinned
 
 
 def closed_form(state, slots, lens, now):
