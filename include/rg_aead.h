@@ -339,6 +339,100 @@ int rg_handshake_resp_batch_dev(rg_ctx *ctx, const rg_hs_peer *peers, uint32_t n
                                 uint8_t *transport_keys /* [n][64]: send key || receive key */,
                                 uint8_t *status, void *stream);
 
+/* ------------------------------ Noise IKpsk2 initiator (batch, async) */
+/* The other end of the handshake: the cryptography of Sessions::new_handshake (rustyguard-core/src/
+ * handshake.rs:260-325) and of handle_handshake_resp (handshake.rs:140-230), so that a handshake can run between
+ * two users of this library.  The conventions are the responder's: all pointers are device memory; the calls
+ * enqueue on `stream` and return without waiting, keep nothing in the context (so they may run on any stream
+ * and be captured into a graph); n == 0 returns RG_OK; RG_EINVAL with nothing enqueued for a null required
+ * pointer, n > 2^32 - 1 or a misaligned array.  Struct rows, desc, messages and transport_keys must be 16-byte
+ * aligned, word arrays (peer_idx, esk, timestamps, session_ids, cookies, pend_table, pend_idx_out, remote_out,
+ * claim) 4-byte aligned.  Session allocation, timers, the peer's endpoint and current_handshake stay with the
+ * caller.
+ *
+ * Randomness and time: the library has no RNG and no clock.  esk[i] must be 32 fresh bytes of the caller's
+ * CSPRNG for every row of every call (EphemeralPrivateKey::generate, handshake.rs:275), never reused;
+ * session_ids[i] is the caller's session index (allocate_session!); timestamps[i] is the caller's TAI64N. */
+typedef struct rg_hs_pending {       /* 128 bytes, 16-byte aligned: SessionHandshake + its session id */
+    uint8_t chain[32], hash[32];     /* HandshakeState after the initiation */
+    uint8_t esk[32];                 /* the initiator's ephemeral private key */
+    uint32_t peer;                   /* row of peers; RG_PEER_NONE = empty, failed or consumed */
+    uint32_t sender;                 /* our session id, msg[4..8] of the initiation */
+    uint8_t pad[24];
+} rg_hs_pending;
+
+/* rg_handshake_initiate_batch_dev: encrypt_handshake_init (rustyguard-crypto/src/lib.rs:287-344) for n rows.
+ * Per row, in this order:
+ *   gate && gate[i] != RG_PKT_OK                       RG_PKT_REJECTED; nothing of the row is read or written
+ *   peer_idx[i] >= npeers                              RG_PKT_INVALID
+ *   es = X25519(esk[i], peer.public_key) all zero      RG_PKT_KEYEXCHANGE
+ *   ss = X25519(own.private_key, peer.public_key)
+ *   all zero                                           RG_PKT_KEYEXCHANGE
+ *   otherwise                                          RG_PKT_OK: messages[i] = the 148-byte HandshakeInit
+ *       le32(1) || session_ids[i] || X25519(esk[i], 9) || sealed own.public_key (48) || sealed timestamps[i]
+ *       (28) || mac1 || mac2 (12 zero bytes behind it), mac1 under peers[p].mac1_key over bytes 0..116, mac2
+ *       under cookies[i] over bytes 0..132 when cookies && has_cookie[i], else zero; pending[i] = the
+ *       handshake state, esk[i], p and session_ids[i].
+ * On a failure the message row is 160 zero bytes and the pending row is zero with peer = RG_PEER_NONE; a lane
+ * stores its status after its rows.  has_cookie is required with cookies.  The per-peer ss secret is computed
+ * by every row (no secret table in this interface). */
+int rg_handshake_initiate_batch_dev(rg_ctx *ctx, const rg_hs_static *own, const rg_hs_peer *peers, uint32_t npeers,
+                                    const uint32_t *peer_idx /* [n] */, const uint8_t *gate /* [n] or NULL */,
+                                    const uint8_t *esk /* [n][32] */, const uint8_t *timestamps /* [n][12] TAI64N */,
+                                    const uint32_t *session_ids /* [n] */,
+                                    const uint8_t *cookies /* [n][16] or NULL */,
+                                    const uint8_t *has_cookie /* [n], required with cookies */, size_t n,
+                                    uint8_t *messages /* [n][160], 16-byte aligned, 148 bytes used */,
+                                    rg_hs_pending *pending /* [n] */, uint8_t *status, void *stream);
+
+/* rg_handshake_finish_batch_dev: decrypt_handshake_resp (lib.rs:435-465) and HandshakeState::split(true)
+ * (prim.rs:299-313) for n messages against npending pending rows.  pend_table maps a receiver id (the
+ * `sender` of a pending row) to its row: an rg_rx_table_build table over those words.  desc[i]: offset, len =
+ * whole message.  Per message, in this order:
+ *   offset % 16 != 0                                   RG_PKT_UNALIGNED
+ *   frame outside [buf, buf + buf_len), or len != 92   RG_PKT_INVALID
+ *   gate && gate[i] != RG_PKT_OK, or
+ *   key_idx == RG_KEY_SKIP                             RG_PKT_REJECTED, message not read
+ *   type word != 2                                     RG_PKT_INVALID
+ *   msg[8..12] not in pend_table, or its row's
+ *   peer == RG_PEER_NONE                               RG_PKT_REJECTED (handshake.rs:171-189: no session, or
+ *                                                      one already past the handshake)
+ *   table row >= npending, or the row's peer >= npeers RG_PKT_INVALID
+ *   ee = X25519(pending.esk, msg[12..44]) all zero     RG_PKT_KEYEXCHANGE
+ *   se = X25519(own.private_key, msg[12..44]) all zero RG_PKT_KEYEXCHANGE
+ *   the empty field's tag fails                        RG_PKT_DECRYPT_ERR
+ *   a lower-indexed message of this batch finished
+ *   the same pending row                               RG_PKT_REJECTED
+ *   otherwise                                          RG_PKT_OK: transport_keys[i] = send key || receive key
+ *       (send = the new chain, receive = HKDF's second output: the mirror of the response call's row),
+ *       pend_idx_out[i] = the pending row, remote_out[i] = msg[4..8] -- what rg_sessions_insert takes -- and
+ *       the pending row is wiped (zeros, peer = RG_PEER_NONE: hs.zeroize()), so a row is consumed once.
+ * On a failure the key row is zero, pend_idx_out[i] = RG_PEER_NONE and remote_out[i] = 0.  mac1 and mac2 are
+ * NOT checked here: run rg_cookie_reply_batch_dev first and pass its status as gate.  buf is never written.
+ *
+ * "First finisher wins" is the reference's in-order loop; here it takes two launches and no ordering by
+ * arrival.  The call fills claim[npending] (a workspace of the call) with 0xFFFFFFFF; the finish kernel reads
+ * pending rows and never writes them, leaves every message whose tag opened at RG_PKT_PENDING and takes
+ * atomicMin(&claim[row], i); a commit kernel then gives RG_PKT_OK to the lane with claim[row] == i, which
+ * wipes the row, and RG_PKT_REJECTED (zero outputs) to every other pending lane.  A minimum does not depend
+ * on the order the lanes arrive in, so the result is deterministic, and nothing reads RG_PKT_OK before the
+ * lane that decided it wrote it.
+ *
+ * One deliberate difference from the reference: decrypt_handshake_resp mixes into the session's
+ * HandshakeState in place before it can fail, so there a response that fails its tag leaves the pending
+ * handshake corrupted.  Here a failing message leaves the pending row untouched, and a later valid response,
+ * in this batch or the next, still finishes it: a forged response must not be able to kill a handshake, and
+ * the corrupted state would depend on the order of arrival.
+ *
+ * RG_EINVAL also for pend_cap not a power of two. */
+int rg_handshake_finish_batch_dev(rg_ctx *ctx, const rg_hs_static *own, const rg_hs_peer *peers, uint32_t npeers,
+                                  const rg_rx_entry *pend_table, uint32_t pend_cap, rg_hs_pending *pending,
+                                  uint32_t npending, const rg_pkt_desc *desc, const uint8_t *gate /* [n] or NULL */,
+                                  size_t n, const uint8_t *buf, size_t buf_len,
+                                  uint8_t *transport_keys /* [n][64]: send key || receive key */,
+                                  uint32_t *pend_idx_out /* [n] */, uint32_t *remote_out /* [n] */,
+                                  uint32_t *claim /* [npending] workspace */, uint8_t *status, void *stream);
+
 /* Tuning knobs.  lanes: lanes cooperating on one packet (0 = automatic, else
  * 1/2/4).  wg_per_cu: resident 256-thread workgroups per CU of the persistent
  * grid (0 = automatic, -1 = plain one-shot grid). */

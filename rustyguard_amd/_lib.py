@@ -45,6 +45,10 @@ SIGNATURES = {
                                             c_vp, c_vp, c_vp]),
     "rg_handshake_resp_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp,
                                             c_vp, c_vp]),
+    "rg_handshake_initiate_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                                c_size, c_vp, c_vp, c_vp, c_vp]),
+    "rg_handshake_finish_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_size,
+                                              c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "rg_rx_table_build": (c_int, [c_vp, c_vp, c_size, c_vp, ctypes.c_uint32]),
     "rg_rx_table_find": (ctypes.c_int64, [c_vp, ctypes.c_uint32, ctypes.c_uint32]),
     "rg_open_batch_dev_rx": (c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, ctypes.c_uint32, c_vp, c_size, c_vp, c_size,

@@ -13,6 +13,9 @@ Reference interface -> this module
   HasMac::verify (overload) + Sessions::write_cookie_message
     (rustyguard-crypto/src/lib.rs:114-140, rustyguard-core/src/lib.rs:517-540)
                                          -> Engine.cookie_reply_dev, encode_src_addr
+  encrypt_handshake_init (lib.rs:287-344), decrypt_handshake_resp + split(true)
+    (lib.rs:435-465)                     -> Engine.handshake_initiate_dev,
+                                            handshake_finish_dev, pending_table
   batched hot path                        -> Engine.seal_dev/open_dev (device
                                              tensors), seal_host/open_host (numpy)
   Sessions send/recv of data frames       -> Sessions.send_batch / recv_batch
@@ -261,6 +264,45 @@ class Engine:
                                                         _vp(has_cookie), n, _vp(responses), _vp(transport_keys),
                                                         _vp(status), _stream_handle(stream)),
                     "rg_handshake_resp_batch_dev")
+
+    def handshake_initiate_dev(self, own, peers, peer_idx, gate, esk, timestamps, session_ids, cookies, has_cookie,
+                               messages, pending, status, stream=None):
+        """encrypt_handshake_init for a batch of rows (rg_handshake_initiate_batch_dev): own = one rg_hs_static,
+        peers = rg_hs_peer rows, peer_idx = uint32 per row, gate = one status byte per row or None, esk = 32 fresh
+        bytes of the caller's CSPRNG per row, timestamps = 12 bytes (TAI64N) per row, session_ids = uint32 per
+        row, cookies = 16 bytes per row with has_cookie = one byte per row (or both None), messages = 160 bytes
+        per row (148 used), pending = HsPending rows (128 bytes): what handshake_finish_dev consumes."""
+        n = _nbytes(status)
+        assert _nbytes(own) == 64 and _nbytes(peers) % 96 == 0 and _nbytes(peer_idx) >= 4 * n
+        assert _nbytes(esk) >= 32 * n and _nbytes(timestamps) >= 12 * n and _nbytes(session_ids) >= 4 * n
+        assert _nbytes(messages) >= 160 * n and _nbytes(pending) >= 128 * n and (gate is None or _nbytes(gate) >= n)
+        assert (cookies is None and has_cookie is None) or (_nbytes(cookies) >= 16 * n and _nbytes(has_cookie) >= n)
+        self._check(self._L.rg_handshake_initiate_batch_dev(self._h, _vp(own), _vp(peers), _nbytes(peers) // 96,
+                                                            _vp(peer_idx), _vp(gate), _vp(esk), _vp(timestamps),
+                                                            _vp(session_ids), _vp(cookies), _vp(has_cookie), n,
+                                                            _vp(messages), _vp(pending), _vp(status),
+                                                            _stream_handle(stream)),
+                    "rg_handshake_initiate_batch_dev")
+
+    def handshake_finish_dev(self, own, peers, pend_table, pending, desc, gate, buf, transport_keys, pend_idx_out,
+                             remote_out, claim, status, stream=None):
+        """decrypt_handshake_resp + split(true) for a batch of responses (rg_handshake_finish_batch_dev):
+        pend_table = pending_table(...) on the device, pending = the HsPending rows of handshake_initiate_dev,
+        gate = one status byte per message (e.g. cookie_reply_dev's output) or None, transport_keys = 64 bytes per
+        message (send key || receive key), pend_idx_out / remote_out = uint32 per message, claim = uint32 per
+        pending row (workspace).  The first valid response of a pending row finishes and wipes it; mac1 / mac2
+        are not checked here."""
+        n = _ndesc(desc)
+        npending = _nbytes(pending) // 128
+        assert _nbytes(own) == 64 and _nbytes(peers) % 96 == 0 and _nbytes(pending) % 128 == 0
+        assert _nbytes(transport_keys) >= 64 * n and _nbytes(pend_idx_out) >= 4 * n and _nbytes(remote_out) >= 4 * n
+        assert _nbytes(claim) >= 4 * npending and _nbytes(status) >= n and (gate is None or _nbytes(gate) >= n)
+        self._check(self._L.rg_handshake_finish_batch_dev(self._h, _vp(own), _vp(peers), _nbytes(peers) // 96,
+                                                          _vp(pend_table), _nbytes(pend_table) // 8, _vp(pending),
+                                                          npending, _vp(desc), _vp(gate), n, _vp(buf), _nbytes(buf),
+                                                          _vp(transport_keys), _vp(pend_idx_out), _vp(remote_out),
+                                                          _vp(claim), _vp(status), _stream_handle(stream)),
+                    "rg_handshake_finish_batch_dev")
 
     def replay_workspace(self, n: int, nwin: int, device=None):
         """The scratch tensor (uint8, on this engine's device) that replay_batch_dev / recv_batch_dev_resident
@@ -801,6 +843,31 @@ def peer_find(peers: np.ndarray, table: np.ndarray, public_key: bytes) -> int:
     pk = np.frombuffer(bytes(public_key), np.uint8)
     assert pk.size == 32
     return int(lib().rg_peer_table_find(_vp(rows), _vp(table), table.shape[0], _vp(pk)))
+
+
+class HsPending(ctypes.Structure):
+    """rg_hs_pending: one pending handshake of the initiator (SessionHandshake + its session id)."""
+    _fields_ = [("chain", ctypes.c_uint8 * 32), ("hash", ctypes.c_uint8 * 32), ("esk", ctypes.c_uint8 * 32),
+                ("peer", ctypes.c_uint32), ("sender", ctypes.c_uint32), ("pad", ctypes.c_uint8 * 24)]
+
+
+def pending_table(pending, cap: int | None = None) -> np.ndarray:
+    """Pending table for handshake_finish_dev (rg_rx_table_build over the rows' `sender` words): uint32 [cap, 2]
+    of (sender, row).  pending: rg_hs_pending rows (uint8 [npending, 128]; rows whose peer is PEER_NONE are left
+    out), or the uint32 session ids handed to handshake_initiate_dev, row = position.  cap a power of two >=
+    2 npending (default: the smallest)."""
+    a = np.asarray(pending)
+    if a.dtype == np.uint8:
+        rows = np.ascontiguousarray(a).reshape(-1, 128)
+        words = rows.view(np.uint32).reshape(-1, 32)
+        live = np.flatnonzero(words[:, 24] != PEER_NONE)
+        senders, n = words[live, 25], len(rows)
+    else:
+        senders = np.ascontiguousarray(a, np.uint32).ravel()
+        live, n = np.arange(len(senders)), len(senders)
+    if cap is None:
+        cap = 1 << max(1, int(2 * n - 1).bit_length())
+    return rx_table(senders, live.astype(np.uint32), cap)
 
 
 def numa_node(engine) -> int:

@@ -25,6 +25,11 @@
          handshakes/s, by stream events, medians of seven with min-max; OpenSSL's X25519 through libcrypto on 1
          and 16 threads beside it when the library is there.  Also written to profiles/handshake_bench.json
 
+  initiator  the batched IKpsk2 initiator at 64 Ki and 1 Ki rows: rg_handshake_initiate_batch_dev,
+         rg_handshake_finish_batch_dev and both, and in the same run the responder calls and rg_x25519_batch_dev
+         on the same handshakes, by stream events, medians of seven with min-max, with each call's time per
+         X25519 ladder.  Also written to profiles/handshake_initiator_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -520,12 +525,107 @@ def handshake_leg(eng):
     return out
 
 
+def initiator_leg(eng):
+    """rg_handshake_initiate_batch_dev and rg_handshake_finish_batch_dev at 64 Ki and 1 Ki rows, and in the same
+    run rg_handshake_init_batch_dev, rg_handshake_resp_batch_dev and rg_x25519_batch_dev on the same handshakes:
+    stream events, medians of seven repetitions with min-max, and the time per X25519 ladder of each call
+    (initiate / 3, finish / 2, init / 2, response / 3).  Written to profiles/handshake_initiator_bench.json."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import handshake_cases as hc  # the Python model makes the keys
+
+    rng = np.random.default_rng(47)
+    rb = lambda k: rng.integers(0, 256, k, dtype=np.uint8).tobytes()  # noqa: E731
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    sk_a, sk_b = rb(32), rb(32)
+    pk_a, pk_b = hc.pubkey(sk_a), hc.pubkey(sk_b)
+    psk = rb(32)
+    others = [hc.pubkey(rb(32)) for _ in range(7)]
+    peers_a = [(pk, rb(32), hc.mac1_key(pk)) for pk in others[:3]] + [(pk_b, psk, hc.mac1_key(pk_b))] + \
+              [(pk, rb(32), hc.mac1_key(pk)) for pk in others[3:]]  # the responder is row 3 of 8
+    peers_b = hc.peer_rows([(pk_a, psk, hc.mac1_key(pk_a))])
+    a_own, a_peers = dev(np.frombuffer(sk_a + pk_a, np.uint8)), dev(hc.peer_rows(peers_a))
+    b_own, b_peers, b_table = dev(np.frombuffer(sk_b + pk_b, np.uint8)), dev(peers_b), dev(aead.peer_table(peers_b))
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    def stats(ts, n, ladders):
+        ts = sorted(ts)
+        med = ts[len(ts) // 2]
+        return {"ms_median": round(med, 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4),
+                "per_s_median": round(n / med * 1e3), "ladders": ladders,
+                "us_per_ladder_row_median": round(med / ladders / n * 1e3, 5),
+                "ms_per_ladder_median": round(med / ladders, 4), "ms_per_ladder_min": round(ts[0] / ladders, 4),
+                "ms_per_ladder_max": round(ts[-1] / ladders, 4)}
+
+    z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")  # noqa: E731
+    out = {}
+    for n in (1 << 16, 1 << 10):
+        sids = np.arange(n, dtype=np.uint32) + 0x100
+        pidx, esk_a, esk_b = dev(np.full(n, 3, np.uint32)), dev(rng.integers(0, 256, (n, 32), dtype=np.uint8)), \
+            dev(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+        ts = dev(np.tile(np.frombuffer(hc.tai64n(1_800_000_000, 7), np.uint8), (n, 1)))
+        d_sid_a, d_sid_b, a_table = dev(sids), dev(sids + 0x4000_0000), dev(aead.pending_table(sids))
+        desc_i, desc_r = np.zeros(n, DESC_DTYPE), np.zeros(n, DESC_DTYPE)
+        desc_i["offset"], desc_i["len"] = np.arange(n, dtype=np.uint64) * 160, 148
+        desc_r["offset"], desc_r["len"] = np.arange(n, dtype=np.uint64) * 96, 92
+        d_desc_i, d_desc_r = dev(desc_i.view(np.uint8).reshape(-1, 16)), dev(desc_r.view(np.uint8).reshape(-1, 16))
+        msgs, pending = z(n, 160), z(n, 128)
+        res, keep_r, resp, keys_b, keys_a = z(n, 128), z(n, 128), z(n, 96), z(n, 64), z(n, 64)
+        st = [z(n) for _ in range(4)]
+        pix, rem, claim = z(n, dtype=torch.int32), z(n, dtype=torch.int32), z(n, dtype=torch.int32)
+        xo, xs, pts = z(n, 32), z(n), dev(rng.integers(0, 256, (n, 32), dtype=np.uint8))
+        ini = lambda: eng.handshake_initiate_dev(a_own, a_peers, pidx, None, esk_a, ts, d_sid_a, None, None, msgs,  # noqa: E731
+                                                 pending, st[0])
+        cons = lambda: eng.handshake_init_dev(b_own, b_peers, b_table, d_desc_i, None, msgs, res, st[1])  # noqa: E731
+        rsp = lambda: eng.handshake_resp_dev(b_peers, res, None, esk_b, d_sid_b, None, None, resp, keys_b, st[2])  # noqa: E731
+        fin = lambda: eng.handshake_finish_dev(a_own, a_peers, a_table, pending, d_desc_r, None, resp, keys_a, pix,  # noqa: E731
+                                               rem, claim, st[3])
+        x = lambda: eng.x25519_dev(esk_a, pts, xo, xs)  # noqa: E731
+        ini(), cons()
+        keep_r.copy_(res)
+        rsp(), fin(), x()
+        torch.cuda.synchronize()
+        assert all((s == aead.PKT_OK).all().item() for s in st)
+        assert torch.equal(keys_a[:, :32], keys_b[:, 32:]) and torch.equal(keys_a[:, 32:], keys_b[:, :32])
+        t = {k: [] for k in ("initiate", "finish", "both", "init", "resp", "x25519")}
+        for _ in range(7):
+            t["initiate"].append(ev_ms(ini))
+            t["finish"].append(ev_ms(fin))  # the rows the initiate call has just written again
+            t["both"].append(ev_ms(lambda: (ini(), fin())))
+            t["init"].append(ev_ms(cons))
+            res.copy_(keep_r)  # the response call consumes its rows: give them back outside the timed window
+            torch.cuda.synchronize()
+            t["resp"].append(ev_ms(rsp))
+            t["x25519"].append(ev_ms(x))
+        assert (st[3] == aead.PKT_OK).all().item()  # every timed finish did the whole work
+        out[f"rows_{n}"] = {"initiate": stats(t["initiate"], n, 3), "finish": stats(t["finish"], n, 2),
+                            "initiate_and_finish": stats(t["both"], n, 5), "init": stats(t["init"], n, 2),
+                            "resp": stats(t["resp"], n, 3), "x25519": stats(t["x25519"], n, 1)}
+    out["note"] = ("stream events around one call each (finish = memset + finish kernel + commit kernel), medians of 7 "
+                   "repetitions after one warm-up round; one initiator with 8 peer rows, every row towards the same "
+                   "responder, fresh ephemeral keys per row; the responder calls run on these handshakes' own "
+                   "messages in the same run; ms_per_ladder = the call's time / its X25519 ladders per row")
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                        "handshake_initiator_bench.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "handshake"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "handshake", "initiator"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
-                      ("replay", replay_leg), ("send", send_leg), ("handshake", handshake_leg)):
+                      ("replay", replay_leg), ("send", send_leg), ("handshake", handshake_leg),
+                      ("initiator", initiator_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
