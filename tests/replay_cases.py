@@ -2,6 +2,7 @@
 -- the host rg_antireplay_would_accept / rg_antireplay_mark_seen through ctypes, packet by packet in array
 order -- and the seeded cases both tests run.  Windows are numpy uint64 [nwin, 33] (32 bitmap words, last: 264 bytes a row)."""
 import ctypes
+import functools
 
 import numpy as np
 
@@ -91,17 +92,16 @@ def edge_cases():
     return out
 
 
-def interleaved(seed, length, nwin=3):
-    """Three windows mixed in one batch, counters drawn around each window's moving edge; about one entry in
-    eight has no window or no verdict to judge.  Returns (windows, win_idx, counters, status)."""
-    rng = np.random.default_rng(seed)
-    W = np.stack([fresh()[0], live(10_000, seed + 1), live(1 << 40, seed + 2)][:nwin])
-    start = [int(W[w, 32]) for w in range(nwin)]
-    edge = list(start)
-    drawn = [[] for _ in range(nwin)]
+def _mix(rng, length, W, rows):
+    """interleaved's traffic over the window rows `rows` of W: counters drawn around each window's moving edge;
+    about one entry in eight has no window or no verdict to judge.  Returns (win_idx, counters, status)."""
+    nwin = len(W)
+    start = {int(w): int(W[w, 32]) for w in rows}
+    edge = dict(start)
+    drawn = {w: [] for w in start}
     widx, ctrs, sts = [], [], []
     for _ in range(length):
-        w = int(rng.integers(0, nwin))
+        w = int(rows[int(rng.integers(0, len(rows)))])
         kind = rng.random()
         if kind < 0.30:
             c = edge[w] + int(rng.integers(1, 9))
@@ -132,7 +132,15 @@ def interleaved(seed, length, nwin=3):
         widx.append(w)
         ctrs.append(c)
         sts.append(st)
-    return W, np.array(widx, np.uint32), np.array(ctrs, np.uint64), np.array(sts, np.uint8)
+    return np.array(widx, np.uint32), np.array(ctrs, np.uint64), np.array(sts, np.uint8)
+
+
+def interleaved(seed, length, nwin=3):
+    """Three windows mixed in one batch, counters drawn around each window's moving edge; about one entry in
+    eight has no window or no verdict to judge.  Returns (windows, win_idx, counters, status)."""
+    rng = np.random.default_rng(seed)
+    W = np.stack([fresh()[0], live(10_000, seed + 1), live(1 << 40, seed + 2)][:nwin])
+    return (W,) + _mix(rng, length, W, np.arange(nwin))
 
 
 INTERLEAVED_LENGTHS = (1, 63, 64, 65, 257, 1025)
@@ -159,3 +167,145 @@ def many_windows(seed=5, nwin=300):
             sts.append(ERR if rng.random() < 0.1 else OK)
     perm = rng.permutation(len(widx))
     return (W, np.array(widx, np.uint32)[perm], np.array(ctrs, np.uint64)[perm], np.array(sts, np.uint8)[perm])
+
+
+# ---- batches large enough for the loops of the grouped scan (csrc/rg_grouped.h) to run more than once
+TILE = 2048  # grouped packets per workgroup of the scans and the radix passes (kGroupTile)
+STRIDE = 2000  # between a window's consecutive counters in `strided`: two of them swapped are >= WINDOW apart
+# (packets, window rows, rows with traffic): the smallest batches at which two radix passes run over three tiles,
+# the radix scan walks two entries a lane, three passes run with three entries a lane, and (CARRY_SIZE) the carry
+# walks two tiles a lane.  test_replay_cpu.py derives these from the numbers.
+LARGE_SIZES = ((4097, 257, 257), (8193, 300, 300), (18433, 70000, 600))
+CARRY_SIZE = (524289, 300, 300)
+
+
+def pool_rows(rng, nwin, pool):
+    """`pool` distinct rows of [0, nwin), sorted.  Rows 0, 255, 256, 257, 65535, 65536 and nwin - 1 are always
+    among them where they exist: every 8-bit digit of the row index is zero for some and non-zero for others."""
+    must = sorted({r for r in (0, 255, 256, 257, 65535, 65536, nwin - 1) if 0 <= r < nwin})
+    assert len(must) <= pool <= nwin
+    if pool == nwin:
+        return np.arange(nwin)
+    rest = np.setdiff1d(np.arange(nwin), must)
+    return np.sort(np.concatenate([must, rng.choice(rest, pool - len(must), replace=False)])).astype(np.int64)
+
+
+def pool_windows(nwin, rows, seed):
+    """nwin windows, all zero but the pool's, which alternate fresh and live as many_windows' do."""
+    W = fresh(nwin)
+    for k, w in enumerate(rows):
+        if k % 2:
+            W[w] = live(5000 + 37 * k, 1000 + 7 * seed + k)
+    return W
+
+
+def heavy_rows(rows):
+    """The two rows a skewed batch favours: neither the first nor the last of the grouped order."""
+    return int(rows[2 * len(rows) // 3]), int(rows[len(rows) // 3])
+
+
+def skewed_rows(rng, length, rows, skew):
+    """A row of `rows` per packet, uniform; skewed: about half of the packets on one row and a quarter on a
+    second, whose grouped runs then span whole tiles without a head in them."""
+    pick = np.asarray(rows)[rng.integers(0, len(rows), length)]
+    if skew:
+        heavy, second = heavy_rows(rows)
+        u = rng.random(length)
+        pick = np.where(u < 0.5, heavy, np.where(u < 0.75, second, pick))
+    return pick.astype(np.uint32)
+
+
+def ranks(rows):
+    """The rank of each packet among the packets of its row, in array order."""
+    rows = np.asarray(rows)
+    n = len(rows)
+    order = np.argsort(rows, kind="stable")
+    s = rows[order]
+    first = np.concatenate([[True], s[1:] != s[:-1]])
+    run_start = np.maximum.accumulate(np.where(first, np.arange(n), 0))
+    r = np.empty(n, np.int64)
+    r[order] = np.arange(n) - run_start
+    return r
+
+
+def pooled(seed, length, nwin, pool):
+    """interleaved's traffic over `pool` of nwin window rows (pool_rows), drawn uniformly."""
+    rng = np.random.default_rng(seed)
+    rows = pool_rows(rng, nwin, pool)
+    W = pool_windows(nwin, rows, seed)
+    return (W,) + _mix(rng, length, W, rows)
+
+
+def strided(seed, length, nwin, pool, skew, mixed=False):
+    """The order-sensitive batch: the packet of rank r (array order) within window w carries L0_w + 1 + STRIDE r
+    and status OK, so a stable grouping accepts every packet and any two packets of a window taken in the wrong
+    order reject the earlier one (it is STRIDE >= WINDOW behind by then).
+    mixed: every packet with i % 7 == 3 is a DECRYPT_ERR, and every packet with i % 11 == 5 repeats the
+    counter of the packet ahead of it in its window."""
+    rng = np.random.default_rng(seed)
+    rows = pool_rows(rng, nwin, pool)
+    W = pool_windows(nwin, rows, seed)
+    widx = skewed_rows(rng, length, rows, skew)
+    r = ranks(widx)
+    sts = np.full(length, OK, np.uint8)
+    if mixed:
+        i = np.arange(length)
+        sts[i % 7 == 3] = ERR
+        r = r - ((i % 11 == 5) & (r > 0))
+    return W, widx, W[widx, 32] + np.uint64(1) + (STRIDE * r).astype(np.uint64), sts
+
+
+BOUNDARY_RUNS = (8, 9, 47, 448, 1536, 2048, 3)
+
+
+def sorted_boundaries(neutral_heads=True):
+    """Sorted windows whose runs begin at 0, 8, 17, 64, 512, 2048 and 4096: on a lane's first packet of the
+    commit's walk (8 consecutive packets a lane), inside a lane, on a wave's first packet and on a tile's.
+    Counters as in `strided`, each run's last packet repeating the one ahead of it.
+    neutral_heads: each run's first packet has status INVALID, so the head of every row is a neutral element
+    (else it is OK and judged against its own window alone)."""
+    widx = np.repeat(np.arange(len(BOUNDARY_RUNS), dtype=np.uint32), BOUNDARY_RUNS)
+    W = pool_windows(len(BOUNDARY_RUNS), np.arange(len(BOUNDARY_RUNS)), 3)
+    r = ranks(widx)
+    ends = np.cumsum(BOUNDARY_RUNS) - 1
+    r[ends] -= 1
+    sts = np.full(len(widx), OK, np.uint8)
+    if neutral_heads:
+        sts[ends - np.array(BOUNDARY_RUNS) + 1] = INVALID
+    return W, widx, W[widx, 32] + np.uint64(1) + (STRIDE * r).astype(np.uint64), sts
+
+
+def same_counter(n=3000):
+    """One window, one counter: [ERR, ERR, OK, OK, ...] with every fifth packet ERR.  Only the first OK packet
+    stays OK; every later OK packet finds it in the (window, counter) table, all of them in one slot."""
+    sts = np.full(n, OK, np.uint8)
+    sts[:2] = ERR
+    sts[::5] = ERR
+    return live(10_000, 7)[None, :], np.zeros(n, np.uint32), np.full(n, 10_005, np.uint64), sts
+
+
+def _large():
+    out = {}
+    for n, nwin, pool in LARGE_SIZES:
+        out[f"pooled-{n}-{nwin}"] = lambda n=n, nwin=nwin, pool=pool: pooled(11, n, nwin, pool)
+        out[f"strided-{n}-{nwin}"] = lambda n=n, nwin=nwin, pool=pool: strided(12, n, nwin, pool, True)
+        out[f"strided_mixed-{n}-{nwin}"] = lambda n=n, nwin=nwin, pool=pool: strided(13, n, nwin, pool, True, True)
+    n, nwin, pool = CARRY_SIZE
+    out[f"strided-{n}-{nwin}"] = lambda: strided(14, n, nwin, pool, True)
+    out["sorted_boundaries"] = sorted_boundaries
+    out["sorted_boundaries_judged_heads"] = lambda: sorted_boundaries(neutral_heads=False)
+    out["same_counter"] = same_counter
+    return out
+
+
+_LARGE = _large()
+LARGE_NAMES = tuple(_LARGE)
+
+
+@functools.lru_cache(maxsize=None)
+def large_case(name):
+    """(windows, win_idx, counters, status) of the named case; built once, not to be written to."""
+    case = _LARGE[name]()
+    for a in case:
+        a.setflags(write=False)
+    return case

@@ -57,15 +57,23 @@ def _ineligible(name, n, nkeys, seed):
     """Every kind of packet that takes no counter, between packets that do."""
     rng = np.random.default_rng(2000 + seed)
     slots = rng.integers(0, nkeys, n).astype(np.uint32)
+    lens = _mix(rng, slots, nkeys, 8)
+    return (name, rows(*[int(x) for x in rng.integers(0, 1 << 34, nkeys)]), slots, lens, T0 + 10)
+
+
+def _mix(rng, slots, nkeys, kinds):
+    """Lengths for `slots`, and one packet in `kinds` of each way to take no counter (written into slots and the
+    lengths): no row, a row out of range, a bad length, no row and a bad length."""
+    n = len(slots)
     lens = (rng.integers(0, 95, n) * 16).astype(np.uint32)
-    kind = rng.integers(0, 8, n)
+    kind = rng.integers(0, kinds, n)
     slots[kind == 0] = SKIP
     slots[kind == 1] = nkeys + rng.integers(0, 1000, int((kind == 1).sum()))
     lens[kind == 2] += rng.integers(1, 16, int((kind == 2).sum())).astype(np.uint32)
     both = kind == 3  # no row and a bad length: REJECTED comes first
     slots[both] = SKIP
     lens[both] += 8
-    return (name, rows(*[int(x) for x in rng.integers(0, 1 << 34, nkeys)]), slots, lens, T0 + 10)
+    return lens
 
 
 def _times(name, n=200):
@@ -105,6 +113,63 @@ def cases():
     lens = np.full(len(slots), 32, np.uint32)
     lens[[0, 64, 512, 2048, 4096]] = 33
     out.append(("sorted_boundaries", rows(1, 2, 3, 4, 5), slots, lens, T0 + 10))
+    return out
+
+
+# ---- batches large enough for the loops of the grouped scan (csrc/rg_grouped.h) to run more than once
+TILE = 2048  # grouped packets per workgroup of the scans and the radix passes (kGroupTile)
+# (packets, state rows, rows with traffic): the smallest batches at which the radix scan walks two entries a
+# lane, three radix passes run with three entries a lane, and the carry walks two tiles a lane.
+# test_send_cpu.py derives these from the numbers.
+LARGE_SIZES = ((8193, 300, 300), (18433, 70000, 600), (524289, 300, 300))
+
+
+def pool_rows(rng, nkeys, pool):
+    """`pool` distinct rows of [0, nkeys), sorted.  Rows 0, 255, 256, 257, 65535, 65536 and nkeys - 1 are always
+    among them where they exist: every 8-bit digit of the row index is zero for some and non-zero for others."""
+    must = sorted({r for r in (0, 255, 256, 257, 65535, 65536, nkeys - 1) if 0 <= r < nkeys})
+    assert len(must) <= pool <= nkeys
+    if pool == nkeys:
+        return np.arange(nkeys)
+    rest = np.setdiff1d(np.arange(nkeys), must)
+    return np.sort(np.concatenate([must, rng.choice(rest, pool - len(must), replace=False)])).astype(np.int64)
+
+
+def heavy_rows(rows):
+    """The two rows a skewed batch favours: neither the first nor the last of the grouped order."""
+    return int(rows[2 * len(rows) // 3]), int(rows[len(rows) // 3])
+
+
+def skewed_rows(rng, n, rows):
+    """A row of `rows` per packet: about half of the packets on one row and a quarter on a second, whose grouped
+    runs then span whole tiles without a head in them; the rest uniform."""
+    heavy, second = heavy_rows(rows)
+    u = rng.random(n)
+    pick = np.asarray(rows)[rng.integers(0, len(rows), n)]
+    return np.where(u < 0.5, heavy, np.where(u < 0.75, second, pick)).astype(np.uint32)
+
+
+def _large(name, n, nkeys, pool, seed, heavy_c0=None):
+    """_ineligible's kinds of packet, one in eight of them, between packets that take counters, over skewed
+    rows.  heavy_c0: the heavy row's starting counter."""
+    rng = np.random.default_rng(3000 + seed)
+    live = pool_rows(rng, nkeys, pool)
+    slots = skewed_rows(rng, n, live)
+    lens = _mix(rng, slots, nkeys, 32)
+    state = np.empty((nkeys, 3), np.uint64)
+    state[:, 0] = rng.integers(0, 1 << 34, nkeys)
+    state[:, 1:] = (T0, T0 + 5)
+    if heavy_c0 is not None:
+        state[heavy_rows(live)[0], 0] = heavy_c0
+    return (name, state, slots, lens, T0 + 10)
+
+
+def large_cases():
+    out = [_large(f"large_{n}_rows_{nkeys}", n, nkeys, pool, k) for k, (n, nkeys, pool) in enumerate(LARGE_SIZES)]
+    # the heavy row runs out 900 counters in, tiles past the one its run begins in: ranks meet the row's room
+    # behind the carry
+    n, nkeys, pool = LARGE_SIZES[0]
+    out.append(_large(f"large_{n}_rows_{nkeys}_reject_edge", n, nkeys, pool, 7, heavy_c0=REJECT - 900))
     return out
 
 

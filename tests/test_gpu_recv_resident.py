@@ -20,7 +20,7 @@ KEYS = np.random.default_rng(21).integers(0, 256, (2, 32), dtype=np.uint8)
 UNALIGNED, NOT_DATA = 4, 5
 
 
-def _seal(specs, rng):
+def _seal(specs, rng, keys=KEYS, recv=RECV):
     """specs: (session, counter, payload bytes) -> list of sealed frames (uint8 arrays)."""
     desc = np.zeros(len(specs), DESC_DTYPE)
     off = 0
@@ -28,7 +28,7 @@ def _seal(specs, rng):
         desc[i] = (off, p, s)
         off += p + 32
     buf = rng.integers(0, 256, off, dtype=np.uint8)
-    oracle.seal_batch(KEYS, RECV, desc, np.array([c for _, c, _ in specs], np.uint64), buf)
+    oracle.seal_batch(keys, recv, desc, np.array([c for _, c, _ in specs], np.uint64), buf)
     return [buf[int(d["offset"]):int(d["offset"]) + int(d["len"]) + 32].copy() for d in desc]
 
 
@@ -70,11 +70,11 @@ def traffic():
     return d1, b1, d2, b2
 
 
-def _model(windows, desc, buf):
+def _model(windows, desc, buf, keys=KEYS, recv=RECV):
     """Final statuses, expected buffer, windows, counters and key rows for one call."""
     opened = buf.copy()
-    st, ctr, kidx = oracle.open_batch_rx(KEYS, RECV, desc, opened)
-    widx = np.where(kidx < len(RECV), kidx, rc.SKIP).astype(np.uint32)
+    st, ctr, kidx = oracle.open_batch_rx(keys, recv, desc, opened)
+    widx = np.where(kidx < len(recv), kidx, rc.SKIP).astype(np.uint32)
     fin, undo, W, _ = rc.host_commit(windows, widx, ctr, st)
     want = buf.copy()
     for i, d in enumerate(desc):
@@ -85,12 +85,14 @@ def _model(windows, desc, buf):
 
 
 class Dev:
-    def __init__(self, engine, n):
+    def __init__(self, engine, n, keys=KEYS, recv=RECV):
         self.engine = engine
-        self.keys = torch.from_numpy(KEYS.copy()).cuda()
-        self.rx = torch.from_numpy(aead.rx_table(RECV, np.arange(2, dtype=np.uint32)).view(np.int32).copy()).cuda()
-        self.win = torch.zeros(2 * 33, dtype=torch.int64, device="cuda")
-        self.ws = engine.replay_workspace(n, 2)
+        self.nkeys = len(recv)
+        self.keys = torch.from_numpy(keys.copy()).cuda()
+        table = aead.rx_table(recv, np.arange(self.nkeys, dtype=np.uint32))
+        self.rx = torch.from_numpy(table.view(np.int32).copy()).cuda()
+        self.win = torch.zeros(self.nkeys * 33, dtype=torch.int64, device="cuda")
+        self.ws = engine.replay_workspace(n, self.nkeys)
 
     def recv(self, desc, buf, stream=None):
         n = len(desc)
@@ -105,7 +107,7 @@ class Dev:
         return (st.cpu().numpy(), db.cpu().numpy(), ctr.cpu().numpy().view(np.uint64), key.cpu().numpy().view(np.uint32))
 
     def windows(self):
-        return self.win.cpu().numpy().view(np.uint64).reshape(2, 33)
+        return self.win.cpu().numpy().view(np.uint64).reshape(self.nkeys, 33)
 
     def working_keys(self, n):
         return self.ws[:16 * n].cpu().numpy().view(DESC_DTYPE)["key_idx"]
@@ -140,6 +142,71 @@ def test_outcome_coverage(engine, traffic):
     assert data.sum() >= 40 and (st[data] == rc.REJECTED).all()
     assert np.array_equal(got, b2) and np.array_equal(dev.windows(), W)
     assert (dev.working_keys(48)[data] == rc.SKIP).all()
+
+
+def _many_sessions(n=4100, nsess=300, seed=23):
+    """n frames of 16-byte payload over nsess sessions (two radix passes over three tiles in the commit): per
+    session mostly ascending counters; repeated frames; jumps ahead followed by the frames 1984 and 1983 behind;
+    about one frame in twenty with a forged tag or ciphertext, its genuine twin right behind it or ahead of it.
+    -> (keys, receiver ids, desc, buf, forged)"""
+    rng = np.random.default_rng(seed)
+    keys = rng.integers(0, 256, (nsess, 32), dtype=np.uint8)
+    recv = (0x1000 + 7 * rng.permutation(nsess)).astype(np.uint32)
+    specs, seq = [], []  # frames to seal: (session, counter, 16); the batch: (index into specs, forged)
+    edge, mine = [0] * nsess, [[] for _ in range(nsess)]
+
+    def new(s, c):
+        specs.append((s, c, 16))
+        mine[s].append(len(specs) - 1)
+        edge[s] = max(edge[s], c)
+        return len(specs) - 1
+
+    while len(seq) < n:
+        s = int(rng.integers(0, nsess))
+        kind = rng.random()
+        if kind < 0.10 and mine[s]:
+            seq.append((mine[s][int(rng.integers(0, len(mine[s])))], False))
+        elif kind < 0.15:
+            f = new(s, edge[s] + int(rng.integers(1, 4)))
+            seq += [(f, True), (f, False)] if rng.random() < 0.5 else [(f, False), (f, True)]
+        elif kind < 0.18:
+            top = edge[s] + 3000
+            seq += [(new(s, top), False), (new(s, top - 1984), False), (new(s, top - 1983), False)]
+        else:
+            seq.append((new(s, edge[s] + int(rng.integers(1, 4))), False))
+    seq = seq[:n]
+    sealed = _seal(specs, rng, keys, recv)
+    frames = []
+    for f, forged in seq:
+        fr = sealed[f].copy()
+        if forged:
+            fr[int(rng.integers(16, 48))] ^= 1 << int(rng.integers(0, 8))  # ciphertext or tag
+        frames.append(fr)
+    desc, buf = _pack(frames)
+    return keys, recv, desc, buf, np.array([forged for _, forged in seq])
+
+
+def test_many_sessions_beyond_one_tile(engine):
+    """4100 frames over 300 sessions: the commit groups by two radix passes over three tiles, and every byte of
+    300 windows is the model's.  Then the same batch again: all of it is stale."""
+    keys, recv, desc, buf, forged = _many_sessions()
+    n, nsess = len(desc), len(recv)
+    fin, want, W, ctr, kidx = _model(rc.fresh(nsess), desc, buf, keys, recv)
+    # what the batch is there for, from the model alone
+    assert (kidx < nsess).all() and len(np.unique(kidx)) == nsess
+    assert 0.03 < forged.mean() < 0.07 and (fin[forged] != rc.OK).all()
+    assert {rc.OK, rc.ERR, rc.REJECTED} == set(fin)
+    assert (fin == rc.ERR).sum() > 50 and (fin[~forged] == rc.REJECTED).sum() > 300
+    dev = Dev(engine, n, keys, recv)
+    st, got, gctr, gkey = dev.recv(desc, buf)
+    assert np.array_equal(st, fin), np.nonzero(st != fin)[0][:10]
+    assert np.array_equal(got, want)
+    assert np.array_equal(dev.windows(), W)
+    assert np.array_equal(gkey, kidx) and np.array_equal(gctr, ctr)
+    st, got, _, gkey = dev.recv(desc, buf)
+    assert np.array_equal(gkey, kidx) and (st == rc.REJECTED).all()
+    assert np.array_equal(got, buf) and np.array_equal(dev.windows(), W)
+    assert (dev.working_keys(n) == rc.SKIP).all()
 
 
 @pytest.mark.parametrize("family", [0, 1, 3])

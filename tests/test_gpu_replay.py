@@ -100,6 +100,20 @@ def test_interleaved_windows_beyond_one_tile(engine):
     check(engine, rc.interleaved(0, 4100))
 
 
+@pytest.mark.parametrize("name", rc.LARGE_NAMES)
+def test_large(engine, name):
+    """The loops of the grouped scan that run more than once (replay_cases.LARGE_SIZES; test_replay_cpu.py shows
+    which loop each size reaches and that the cases hold what they are for): the radix scan with two and three
+    entries a lane, two and three radix passes over several tiles, the carry with two tiles a lane, rows whose
+    grouped runs span whole tiles, heads on the boundaries of the commit's walk, one contended table slot."""
+    case = rc.large_case(name)
+    st, _, _ = check(engine, case)
+    if name.startswith("strided-"):
+        assert (st == rc.OK).all()  # the grouping kept every window's packets in array order
+    if name == "same_counter":
+        assert list(st[:3]) == [rc.ERR, rc.ERR, rc.OK] and (st[3:] == rc.REJECTED).all()
+
+
 def test_many_windows_few_packets(engine):
     check(engine, rc.many_windows())
 

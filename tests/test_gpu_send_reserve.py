@@ -60,8 +60,7 @@ def _compare(got, want):
     assert np.array_equal(S, S_w), np.nonzero((S != S_w).any(axis=1))[0][:10]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: c[0])
-def test_case(engine, case):
+def _run(engine, case):
     name, state, slots, lens, now = case
     want = sc.loop(state, slots, lens, now)
     d = Dev(state, slots, lens, now)
@@ -73,6 +72,21 @@ def test_case(engine, case):
     assert np.array_equal(work["offset"], d.desc["offset"]) and np.array_equal(work["len"], d.desc["len"])
     took = want[0] == sc.PENDING
     assert np.array_equal(work["key_idx"], np.where(took, np.asarray(slots, np.uint32), sc.SKIP))
+    return d, took
+
+
+@pytest.mark.parametrize("case", sc.large_cases(), ids=lambda c: c[0])
+def test_large_case(engine, case):
+    """The loops of the grouped scan that run more than once (send_cases.LARGE_SIZES; test_send_cpu.py shows
+    which loop each size reaches): the radix scan with two and three entries a lane, two and three radix passes
+    over several tiles, the carry with two tiles a lane, rows whose grouped runs span whole tiles."""
+    _run(engine, case)
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c[0])
+def test_case(engine, case):
+    name, state, slots, lens, now = case
+    d, took = _run(engine, case)
     if name == "rekey_edge":
         assert list(d.rekey.cpu().numpy()) == sc.expect_rekey_edge()
     if name == "reject_edge_8300":

@@ -32,7 +32,7 @@ def _i64(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.uint64).view(np.int64).copy()).cuda()
 
 
-def _model(state, slots, desc, buf, now):
+def _model(state, slots, desc, buf, now, keys=KEYS, recv=RECV):
     """-> (final status, counters, rekey, state', frames) for descriptors that all lie in the buffer, aligned."""
     st, ctr, rk, S = sc.loop(state, slots, desc["len"], now)
     took = st == sc.PENDING
@@ -40,17 +40,18 @@ def _model(state, slots, desc, buf, now):
     if took.any():
         d = desc[took].copy()
         d["key_idx"] = np.asarray(slots, np.uint32)[took]
-        oracle.seal_batch(KEYS, RECV, d, ctr[took], want)
+        oracle.seal_batch(keys, recv, d, ctr[took], want)
     return np.where(took, sc.OK, st).astype(np.uint8), ctr, rk, S, want
 
 
 class Dev:
-    def __init__(self, engine, state, n):
+    def __init__(self, engine, state, n, keys=KEYS, recv=RECV):
         self.engine = engine
-        self.keys = torch.from_numpy(KEYS.copy()).cuda()
-        self.recv = torch.from_numpy(RECV.view(np.int32).copy()).cuda()
+        self.model_keys = keys, recv
+        self.keys = torch.from_numpy(keys.copy()).cuda()
+        self.recv = torch.from_numpy(recv.view(np.int32).copy()).cuda()
         self.state = _i64(np.asarray(state, np.uint64).reshape(-1))
-        self.ws = engine.send_workspace(n, NK)
+        self.ws = engine.send_workspace(n, len(recv))
 
     def send(self, slots, desc, buf, now, stream=None, outputs=True):
         n = len(desc)
@@ -85,7 +86,7 @@ def _traffic(n, seed, ineligible=True):
 
 
 def _check(dev, state, slots, desc, buf, now, outputs=True):
-    fin, ctr, rk, S, want = _model(state, slots, desc, buf, now)
+    fin, ctr, rk, S, want = _model(state, slots, desc, buf, now, *dev.model_keys)
     st, gctr, grk, got = dev.send(slots, desc, buf, now, outputs=outputs)
     assert np.array_equal(st, fin), np.nonzero(st != fin)[0][:10]
     if outputs:
@@ -126,6 +127,26 @@ def test_sizes(engine, n, nrows):
     dev = Dev(engine, state, n)
     fin, _ = _check(dev, state, slots, desc, buf, sc.T0 + 9)
     assert (fin == sc.OK).all()
+
+
+def test_size_8193_rows_300(engine):
+    """Two radix passes over five tiles, the radix scan with two entries a lane (send_cases.LARGE_SIZES), then
+    the seal: 300 keys, rows skewed so that one row's grouped run spans whole tiles."""
+    n, nrows = 8193, 300
+    rng = np.random.default_rng(61)
+    keys = rng.integers(0, 256, (nrows, 32), dtype=np.uint8)
+    recv = (0x1000 + 7 * rng.permutation(nrows)).astype(np.uint32)
+    sizes = rng.choice((16, 32, 48), n).astype(np.uint32)
+    slots = sc.skewed_rows(rng, n, np.arange(nrows))
+    desc, buf = _frames(sizes, rng)
+    state = np.empty((nrows, 3), np.uint64)
+    state[:, 0] = rng.integers(0, 1 << 40, nrows)
+    state[:, 1:] = sc.T0
+    state[sc.heavy_rows(np.arange(nrows))[0], 0] = (1 << 32) - 100  # the heavy row's counters cross 2^32
+    dev = Dev(engine, state, n, keys, recv)
+    fin, S = _check(dev, state, slots, desc, buf, sc.T0 + 9)
+    assert (fin == sc.OK).all() and len(np.unique(slots)) == nrows
+    assert int(S[:, 0].sum() - state[:, 0].sum()) == n and int(np.bincount(slots).max()) > n // 2 - 200
 
 
 def test_optional_outputs_and_no_clock(engine):

@@ -149,3 +149,126 @@ def test_closed_form_interleaved(seed, length):
 
 def test_closed_form_many_windows():
     _same(rc.many_windows())
+
+
+# ---- the cases that run the grouped scan's loops more than once (replay_cases.large_case)
+@pytest.fixture(scope="module")
+def model():
+    """name -> host_commit's result, computed once per case."""
+    done = {}
+
+    def get(name):
+        if name not in done:
+            done[name] = rc.host_commit(*rc.large_case(name))
+        return done[name]
+
+    return get
+
+
+@pytest.mark.parametrize("name", rc.LARGE_NAMES)
+def test_closed_form_large(model, name):
+    W, widx, ctrs, sts = rc.large_case(name)
+    st_h, undo_h, W_h, _ = model(name)
+    st_c, undo_c, W_c = closed_form(W, widx, ctrs, sts)
+    assert np.array_equal(st_c, st_h) and np.array_equal(undo_c, undo_h) and np.array_equal(W_c, W_h)
+
+
+def _loops(n, nrows):
+    """(tiles, radix passes, entries a lane of the radix scan, tiles a lane of the carry) of a batch: the
+    arithmetic of csrc/rg_grouped.h restated."""
+    nblk = -(-n // rc.TILE)
+    passes = 0 if nrows <= 1 else -(-(nrows - 1).bit_length() // 8)
+    return nblk, passes, -(-256 * nblk // 1024), -(-nblk // 256)
+
+
+def test_large_sizes_reach_their_loops():
+    assert [_loops(n, nwin) for n, nwin, _ in rc.LARGE_SIZES] == [(3, 2, 1, 1), (5, 2, 2, 1), (10, 3, 3, 1)]
+    assert _loops(*rc.CARRY_SIZE[:2]) == (257, 2, 65, 2)
+    # each is the smallest: one packet or one row fewer and the loop named in replay_cases runs once less
+    assert _loops(4096, 257)[0] == 2 and _loops(4097, 256)[1] == 1
+    assert _loops(8192, 300)[2] == 1
+    assert _loops(18433, 65536)[1] == 2
+    assert _loops(524288, 300)[3] == 1
+    # 18433 is the first size whose scan, at three entries a lane, ends on a lane holding one entry; the
+    # carry's last busy lane at 524289 holds one tile
+    assert 256 * 10 == 853 * 3 + 1 and _loops(18432, 70000)[2] == 3 and 256 * 9 == 768 * 3
+    assert 257 == 128 * 2 + 1
+    # what the suite had before: one entry and one tile a lane wherever a radix pass ran
+    assert _loops(4100, 3)[1:] == (1, 1, 1) and _loops(8300, 1)[1] == 0
+
+
+@pytest.mark.parametrize("n,nwin,pool", rc.LARGE_SIZES)
+def test_pooled_reaches_every_outcome_and_digit(model, n, nwin, pool):
+    name = f"pooled-{n}-{nwin}"
+    W, widx, _, sts = rc.large_case(name)
+    shares = rc.class_shares(model(name)[3])
+    print(f"{name}: " + ", ".join(f"{k} {v:.3f}" for k, v in shares.items()))
+    assert min(shares.values()) >= rc.MIN_SHARE, shares
+    assert (widx == rc.SKIP).any() and ((widx != rc.SKIP) & (widx >= nwin)).any() and (sts > rc.ERR).any()
+    rows = np.unique(widx[widx < nwin])
+    assert len(rows) == pool and not W[np.setdiff1d(np.arange(nwin), rows)].any()
+    assert set(rows) >= {r for r in (0, 255, 256, 257, 65535, 65536, nwin - 1) if r < nwin}
+    for shift in range(0, 8 * _loops(n, nwin)[1], 8):  # every digit a radix pass sorts by: zero and not
+        digit = (rows >> shift) & 255
+        assert (digit == 0).any() and (digit != 0).any(), shift
+
+
+def _heavy(widx):
+    """(row, packets, whole tiles of its grouped run) of the row with most packets, from the row counts."""
+    rows, counts = np.unique(widx, return_counts=True)
+    k = int(np.argmax(counts))
+    start = int(counts[:k].sum())  # the grouped order is by row, and every packet here has one
+    end = start + int(counts[k])
+    return int(rows[k]), int(counts[k]), max(0, end // rc.TILE - -(-start // rc.TILE))
+
+
+@pytest.mark.parametrize("n,nwin,pool", rc.LARGE_SIZES + (rc.CARRY_SIZE,))
+def test_strided_is_order_sensitive(model, n, nwin, pool):
+    name = f"strided-{n}-{nwin}"
+    W, widx, ctrs, sts = rc.large_case(name)
+    st, undo, _, _ = model(name)
+    assert (sts == rc.OK).all() and (st == rc.OK).all() and not undo.any()
+    row, count, tiles = _heavy(widx)
+    print(f"{name}: row {row} holds {count} packets, {tiles} whole tiles of the grouped order")
+    assert tiles >= {8193: 1, 524289: 100}.get(n, 0)
+    # two neighbouring packets of the heavy window the other way round: the model rejects the later one
+    mine = np.nonzero(widx == row)[0][:64]
+    c = ctrs[mine].copy()
+    c[[30, 31]] = c[[31, 30]]
+    st2 = rc.host_commit(W, widx[mine], c, sts[mine])[0]
+    assert list(np.nonzero(st2 == rc.REJECTED)[0]) == [31]
+
+
+@pytest.mark.parametrize("n,nwin,pool", rc.LARGE_SIZES)
+def test_strided_mixed_outcomes(model, n, nwin, pool):
+    name = f"strided_mixed-{n}-{nwin}"
+    _, widx, _, sts = rc.large_case(name)
+    shares = rc.class_shares(model(name)[3])
+    print(f"{name}: " + ", ".join(f"{k} {v:.3f}" for k, v in shares.items()))
+    assert shares["accepted"] > 0.7 and shares["duplicate"] > 0.05 and shares["bad_tag_kept"] > 0.1
+    assert shares["too_old"] == 0  # nothing is out of order in the array
+    assert _heavy(widx)[2] >= (1 if n >= 8193 else 0)
+
+
+def test_sorted_boundaries_and_same_counter_shapes(model):
+    for name, head in (("sorted_boundaries", rc.INVALID), ("sorted_boundaries_judged_heads", rc.OK)):
+        _, widx, ctrs, sts = rc.large_case(name)
+        heads = np.nonzero(np.concatenate([[True], widx[1:] != widx[:-1]]))[0]
+        assert list(heads) == [0, 8, 17, 64, 512, 2048, 4096] and len(widx) == 4099
+        st = model(name)[0]
+        assert (sts[heads] == head).all() and (st[heads] == head).all()
+        tails = np.concatenate([heads[1:], [len(widx)]]) - 1
+        assert (st[tails] == rc.REJECTED).all() and (ctrs[tails] == ctrs[tails - 1]).all()
+        rest = np.setdiff1d(np.arange(len(widx)), np.concatenate([heads, tails]))
+        assert (st[rest] == rc.OK).all()
+        if head == rc.OK:
+            # a head judged against the maximum of the row ahead of it, not against its own window alone, would
+            # be too old: that maximum lies above the head's window and WINDOW or more above its counter
+            W = rc.large_case(name)[0]
+            for k in range(1, len(heads)):
+                ahead = int(ctrs[heads[k] - 1])
+                assert ahead > int(W[k, 32]) and ahead - int(ctrs[heads[k]]) >= rc.WINDOW, k
+    _, _, _, sts = rc.large_case("same_counter")
+    st = model("same_counter")[0]
+    assert list(sts[:7]) == [rc.ERR, rc.ERR, rc.OK, rc.OK, rc.OK, rc.ERR, rc.OK]
+    assert list(st[:3]) == [rc.ERR, rc.ERR, rc.OK] and (st[3:] == rc.REJECTED).all() and len(st) == 3000

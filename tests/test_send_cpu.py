@@ -138,3 +138,73 @@ def test_cases_reach_their_edges():
     (_, _, slots, lens, _), (st, _, _, _) = by["ineligible_3rows_700"]
     assert {sc.PENDING, sc.INVALID, sc.REJECTED} == set(st)
     assert (st[(slots == sc.SKIP) & (lens % 16 != 0)] == sc.REJECTED).all()
+
+
+# ---- the cases that run the grouped scan's loops more than once (send_cases.large_cases)
+LARGE = sc.large_cases()
+
+
+@pytest.fixture(scope="module")
+def large_loop():
+    """name -> the loop's result, computed once per case."""
+    return {c[0]: sc.loop(*c[1:]) for c in LARGE}
+
+
+@pytest.mark.parametrize("case", LARGE, ids=lambda c: c[0])
+def test_closed_form_equals_the_loop_large(large_loop, case):
+    name, state, slots, lens, now = case
+    st, ctr, rk, S = large_loop[name]
+    st_c, ctr_c, rk_c, S_c = closed_form(state, slots, lens, now)
+    assert np.array_equal(st_c, st), np.nonzero(st_c != st)[0][:10]
+    assert np.array_equal(ctr_c, ctr) and np.array_equal(rk_c, rk)
+    assert np.array_equal(S_c, S)
+
+
+def _loops(n, nrows):
+    """(tiles, radix passes, entries a lane of the radix scan, tiles a lane of the carry) of a batch: the
+    arithmetic of csrc/rg_grouped.h restated."""
+    nblk = -(-n // sc.TILE)
+    passes = 0 if nrows <= 1 else -(-(nrows - 1).bit_length() // 8)
+    return nblk, passes, -(-256 * nblk // 1024), -(-nblk // 256)
+
+
+def test_large_sizes_reach_their_loops():
+    assert [_loops(n, nkeys) for n, nkeys, _ in sc.LARGE_SIZES] == [(5, 2, 2, 1), (10, 3, 3, 1), (257, 2, 65, 2)]
+    assert _loops(8192, 300)[2] == 1 and _loops(18433, 65536)[1] == 2 and _loops(524288, 300)[3] == 1
+    assert 256 * 10 == 853 * 3 + 1 and 257 == 128 * 2 + 1  # the last busy lane holds one entry, one tile
+    # what the suite had before: no radix pass at 8300 packets, one entry and one tile a lane elsewhere
+    assert _loops(8300, 1)[1] == 0 and _loops(4097, 3)[1:] == (1, 1, 1) and _loops(2500, 300)[1:] == (2, 1, 1)
+
+
+@pytest.mark.parametrize("case", LARGE, ids=lambda c: c[0])
+def test_large_cases_stay_meaningful(large_loop, case):
+    name, state, slots, lens, _ = case
+    st, ctr, _, S = large_loop[name]
+    nkeys = len(state)
+    valid = (slots != sc.SKIP) & (slots < nkeys)
+    rows, counts = np.unique(np.where(valid, slots, 0), return_counts=True)  # the grouping key
+    k = int(np.argmax(counts))
+    heavy = int(rows[k])
+    start = int(counts[:k].sum())
+    tiles = (start + int(counts[k])) // sc.TILE - -(-start // sc.TILE)
+    took = st == sc.PENDING
+    print(f"{name}: {took.mean():.3f} take a counter; row {heavy} holds {counts[k]} packets, {tiles} whole tiles")
+    assert tiles >= (100 if len(slots) == 524289 else 1)
+    assert {sc.PENDING, sc.INVALID, sc.REJECTED} == set(st)
+    assert (slots == sc.SKIP).any() and ((slots != sc.SKIP) & (slots >= nkeys)).any()
+    live = np.unique(slots[valid])
+    for shift in range(0, 8 * _loops(len(slots), nkeys)[1], 8):  # every digit a radix pass sorts by: zero and not
+        assert (((live >> shift) & 255) == 0).any() and (((live >> shift) & 255) != 0).any()
+    if name.endswith("reject_edge"):
+        # the heavy row shuts 900 counters in, and by design takes most of the batch with it: the share is
+        # asked of the other rows
+        mine = valid & (slots == heavy)
+        assert int(state[heavy, 0]) == sc.REJECT - 900 and int(S[heavy, 0]) == sc.REJECT
+        assert took[mine].sum() == 900 and (st[mine] == sc.REJECTED).sum() > 1000
+        last = np.nonzero(mine & took)[0][-1]
+        assert int(ctr[last]) == sc.REJECT - 1
+        # the row's last counter is taken in a later tile of the grouped order than the one its run begins in
+        assert heavy != 0 and (start + int(mine[:last].sum())) // sc.TILE > start // sc.TILE
+        assert took[~mine].mean() >= 0.8
+    else:
+        assert took.mean() >= 0.8
