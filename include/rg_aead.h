@@ -93,6 +93,8 @@ enum rg_pkt_status {
                                a cookie reply was written for this message */
     RG_PKT_KEYEXCHANGE = 8, /* Error::KeyExchangeError: an X25519 result was all zero (rg_x25519_batch_dev and
                                the handshake calls) */
+    RG_PKT_UNROUTABLE = 9,  /* cryptokey routing (rg_route_batch_dev, rg_route_check_batch_dev): the inner address
+                               matches no allowed prefix, or on receive a prefix of another peer */
 };
 
 /* Statuses fail closed.  A packet reads RG_PKT_OK only after the kernel that processed it wrote that
@@ -784,6 +786,103 @@ int rg_send_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, const uint32_t 
                                const uint64_t *now_ns, uint8_t *buf, size_t buf_len, uint8_t *status,
                                uint64_t *counters_out, uint8_t *rekey_out, void *workspace, size_t workspace_len,
                                void *stream);
+
+/* ------------------------------- device-resident cryptokey routing (async) */
+/* The AllowedIPs table in device memory, so that neither direction of the resident transport path reads a
+ * packet header back to the host: handle_intern's peer_net.lookup(&dest) and zero padding
+ * (rustyguard-tun/src/lib.rs:214-243) ahead of the send, handle_extern's source check (:174-202) behind the
+ * receive.  IPv4 only, as the reference (Ipv4LCTrieMap<PeerId>).
+ *
+ * The table is a fixed-stride 16-8-8 multibit trie in uint32_t words (csrc/rg_route.h and DESIGN.md have the
+ * encoding): a root of 65536 entries, child blocks of 256, a lookup of at most three dependent loads.
+ * rg_route_table_words gives the exact size for a prefix array (0 if a row is invalid); rg_route_table_build
+ * writes it into host memory, which the caller uploads.  Lookup is longest-prefix match; no match is
+ * RG_PEER_NONE (the reference's sentinel root); a /0 prefix sets the default; bits of addr below prefix_len are
+ * ignored; the same (network, length) given twice takes the last row's peer; np == 0 gives the all-NONE root.
+ * The build is deterministic: the table is a function of the prefix array.  There is no in-place update:
+ * replacing a table is building another and passing the other pointer from the next batch on.
+ * rg_route_table_build: RG_EINVAL for a null pointer (p may be NULL when np == 0), prefix_len > 32 or
+ * peer > 0x7FFFFFFF; RG_EFULL when cap_words < rg_route_table_words(p, np), nothing written.
+ * rg_route_lookup is the host's lookup (RG_PEER_NONE also for a null pointer or table_words < 65536); the
+ * kernels compile the same text.  Every child index is checked against table_words before it is used, so a
+ * corrupt table can misroute but never makes a lookup read outside the table.
+ *
+ * An inner packet of L bytes is acceptable IPv4 iff L >= 20, the version nibble is 4 and
+ * 20 <= 4 IHL <= total_length <= L (IHL the low nibble of byte 0, total_length bytes 2-3, big endian).
+ *
+ * The device calls follow the two sections above: every pointer is device memory (buf 16-byte aligned), the
+ * calls enqueue on `stream` and return without waiting, allocate nothing and keep nothing in the context (so
+ * they can be captured into a graph).  table_words is the table's size; no lane reads past it.
+ *
+ * rg_route_batch_dev is handle_intern up to send_message.  peer_slot[p] is peer p's current key-table row,
+ * RG_KEY_SKIP = no session.  desc[i].offset is the frame's offset (the inner packet starts at offset + 16),
+ * desc[i].len the UNPADDED inner length L; desc[i].key_idx is ignored.  For every i, independently, the first
+ * rule that applies:
+ *   1. offset % 16 != 0                                          status[i] = RG_PKT_UNALIGNED
+ *   2. offset + 16 + roundup16(L) + 16 > buf_len (64 bits, no wrap)          RG_PKT_INVALID
+ *   3. the packet is not acceptable IPv4                                     RG_PKT_INVALID
+ *   4. peer = lookup(destination, bytes 16-19) is RG_PEER_NONE or >= npeers  RG_PKT_UNROUTABLE
+ *   5. peer_slot[peer] == RG_KEY_SKIP                                        RG_PKT_REJECTED  (no session;
+ *                                   peers_out[i] = peer: whom to start a handshake with)
+ *   6. otherwise RG_PKT_OK: bytes [L, roundup16(L)) of the inner packet are set to zero,
+ *      slots_out[i] = peer_slot[peer], desc_out[i] = {offset, roundup16(L), slots_out[i]}, peers_out[i] = peer
+ * In every other case slots_out[i] = RG_KEY_SKIP, desc_out[i] = {offset, L, RG_KEY_SKIP} and no byte of buf is
+ * written; peers_out[i] = RG_PEER_NONE in cases 1-4.  peers_out may be NULL; desc_out may be desc itself.
+ * slots_out and desc_out are what rg_send_batch_dev_resident takes.
+ *
+ * rg_route_check_batch_dev is the source check of handle_extern, behind rg_recv_batch_dev_resident on the
+ * same stream: desc[n] are the frames' descriptors (offset, frame length W), key_idx[n] what the receive
+ * reported in key_idx_out, slot_peer[k] the peer of key-table row k, buf is only read.  status[n] is updated
+ * in place:
+ *   status[i] != RG_PKT_OK                                   stays; inner_len_out[i] = 0
+ *   W == 32 (a keepalive)                                    stays RG_PKT_OK; inner_len_out[i] = 0
+ *   the W - 32 bytes at offset + 16 are not acceptable IPv4  RG_PKT_INVALID (also a descriptor that is
+ *                                   misaligned, outside buf or has W < 32, which no receive reports as OK)
+ *   lookup(source, bytes 12-15) is RG_PEER_NONE, key_idx[i] >= nkeys,
+ *   or the lookup's peer != slot_peer[key_idx[i]]            RG_PKT_UNROUTABLE
+ *   otherwise                                                stays RG_PKT_OK; inner_len_out[i] = total_length
+ * (inner_len_out[i] = 0 for every packet that does not end RG_PKT_OK).  total_length trims the sender's zero
+ * padding.  inner_len_out may be NULL.  The anti-replay windows are not touched: the reference, too, commits
+ * the counter before this check.
+ *
+ * rg_send_batch_dev_routed is rg_route_batch_dev, writing slots_out and desc_out into the workspace, then
+ * rg_send_batch_dev_resident over them with the same state, now_ns, counters_out and rekey_out, then an overlay:
+ * a packet the route did not route (status != RG_PKT_OK there) keeps the route's status, has taken no counter
+ * and its frame is untouched; every other packet gets the resident send's final verdict.  Frames, statuses,
+ * counters and state rows equal those of the three steps called separately.  The workspace, 16-byte aligned,
+ * of at least rg_route_workspace_size(n, nkeys) bytes (0 when n is too large; non-decreasing in both
+ * arguments), holds the route's arrays -- it begins with the route's n working descriptors -- and the resident
+ * send's workspace.  The one-stream rule of the resident send applies unchanged, as does what it says about
+ * buffers of the context that have to grow.  peers_out, counters_out, rekey_out and now_ns may be NULL.
+ *
+ * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer, n > 2^32 - 1,
+ * table_words < 65536, buf not 16-byte aligned; for the routed send also nkeys == 0, state not 8-byte or
+ * workspace not 16-byte aligned, workspace_len smaller than rg_route_workspace_size reports. */
+typedef struct rg_route_prefix {   /* 12 bytes */
+    uint8_t  addr[4];              /* network order; bits below prefix_len are ignored (masked) */
+    uint32_t prefix_len;           /* 0..32 */
+    uint32_t peer;                 /* <= 0x7FFFFFFF */
+} rg_route_prefix;
+
+size_t rg_route_table_words(const rg_route_prefix *p, uint32_t np);
+int rg_route_table_build(const rg_route_prefix *p, uint32_t np, uint32_t *table, size_t cap_words);
+uint32_t rg_route_lookup(const uint32_t *table, size_t table_words, const uint8_t addr[4]);
+
+size_t rg_route_workspace_size(size_t n, uint32_t nkeys);
+int rg_route_batch_dev(rg_ctx *ctx, const uint32_t *table, size_t table_words, const uint32_t *peer_slot,
+                       uint32_t npeers, const rg_pkt_desc *desc, size_t n, uint8_t *buf, size_t buf_len,
+                       uint32_t *peers_out, uint32_t *slots_out, rg_pkt_desc *desc_out, uint8_t *status,
+                       void *stream);
+int rg_route_check_batch_dev(rg_ctx *ctx, const uint32_t *table, size_t table_words, const uint32_t *slot_peer,
+                             uint32_t nkeys, const rg_pkt_desc *desc, const uint32_t *key_idx, size_t n,
+                             const uint8_t *buf, size_t buf_len, uint8_t *status, uint32_t *inner_len_out,
+                             void *stream);
+int rg_send_batch_dev_routed(rg_ctx *ctx, const uint8_t *keys, const uint32_t *receivers, uint32_t nkeys,
+                             rg_send_state *state, const uint32_t *table, size_t table_words,
+                             const uint32_t *peer_slot, uint32_t npeers, const rg_pkt_desc *desc, size_t n,
+                             const uint64_t *now_ns, uint8_t *buf, size_t buf_len, uint32_t *peers_out,
+                             uint8_t *status, uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
+                             size_t workspace_len, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

@@ -115,6 +115,16 @@ SIGNATURES = {
                                           c_vp]),
     "rg_send_batch_dev_resident": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_size, c_vp,
                                            c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_route_table_words": (c_size, [c_vp, c_u32]),
+    "rg_route_table_build": (c_int, [c_vp, c_u32, c_vp, c_size]),
+    "rg_route_lookup": (c_u32, [c_vp, c_size, c_vp]),
+    "rg_route_workspace_size": (c_size, [c_size, c_u32]),
+    "rg_route_batch_dev": (c_int, [c_vp, c_vp, c_size, c_vp, c_u32, c_vp, c_size, c_vp, c_size, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp]),
+    "rg_route_check_batch_dev": (c_int, [c_vp, c_vp, c_size, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_size, c_vp, c_vp,
+                                         c_vp]),
+    "rg_send_batch_dev_routed": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_u32, c_vp, c_size, c_vp,
+                                         c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

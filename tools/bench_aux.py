@@ -30,6 +30,14 @@
          on the same handshakes, by stream events, medians of seven with min-max, with each call's time per
          X25519 ladder.  Also written to profiles/handshake_initiator_bench.json
 
+  route  cryptokey routing on cfg2 and cfg4 geometry under a table of 256 prefixes of mixed length (/16 to /32,
+         one peer each; cfg4: peer = session, cfg2: every peer on the one session), every packet an IPv4 packet
+         of 1500 bytes: rg_send_batch_dev_routed against rg_send_batch_dev_resident with precomputed slots and
+         padded descriptors on the same plaintext, and rg_recv_batch_dev_resident followed by
+         rg_route_check_batch_dev against rg_recv_batch_dev_resident alone on the same frames; rg_route_batch_dev
+         alone beside them.  Medians of seven with min-max, by stream events and by host wall clock.  Also
+         written to profiles/route_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -42,7 +50,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from rustyguard_amd import aead, workloads  # noqa: E402
+from rustyguard_amd import aead, route, workloads  # noqa: E402
 from rustyguard_amd.device import DeviceBatch  # noqa: E402
 from rustyguard_amd.workloads import DESC_DTYPE  # noqa: E402
 
@@ -379,6 +387,164 @@ def send_leg(eng):
     return res
 
 
+def route_leg(eng):
+    import time
+
+    T = 10**12
+    NP = 256
+    LENS = (16, 20, 24, 28, 32)
+
+    def prefix(p):
+        """peer p's one prefix, in a /16 of its own: (network as bytes, length)"""
+        plen = LENS[p % len(LENS)]
+        host = {16: (0, 0), 20: (64, 0), 24: (77, 0), 28: (77, 16), 32: (77, 5)}[plen]
+        return bytes([10, p, *host]), plen
+
+    def shape(cfg):
+        w = workloads.build(cfg)
+        n, nk = w.n, len(w.receivers)
+        b = DeviceBatch(eng, w)
+        off = w.desc["offset"].astype(np.int64)
+        stride = int(off[1] - off[0])
+        L, P = int(w.inner_len[0]), int(w.desc["len"][0])
+        assert (np.diff(off) == stride).all() and w.buf_bytes >= n * stride and (w.inner_len == L).all()
+        assert (w.desc["len"] == P).all() and P == (L + 15) // 16 * 16
+        rows = lambda t: t[: n * stride].view(n, stride)  # noqa: E731
+        table = torch.from_numpy(route.build_table([(prefix(p), p) for p in range(NP)]).view(np.int32)).cuda()
+        slot = np.ascontiguousarray(w.desc["key_idx"], np.uint32)
+        # cfg4: peer = session; cfg2: the packets go round the 256 peers, which all share the one session
+        peer = slot if nk == NP else (np.arange(n) % NP).astype(np.uint32)
+        peer_slot = np.arange(NP, dtype=np.uint32) if nk == NP else np.zeros(NP, np.uint32)
+        slot_peer = np.arange(nk, dtype=np.uint32)  # the receiving side: key row k is peer k
+        addr = np.array([list(prefix(p)[0]) for p in range(NP)], np.uint8)
+        hdr = np.zeros((n, 20), np.uint8)
+        hdr[:, 0], hdr[:, 2], hdr[:, 3], hdr[:, 8], hdr[:, 9] = 0x45, L >> 8, L & 255, 64, 17
+        hdr[:, 12:16] = addr[slot_peer[slot]]  # a source of the session's own peer
+        hdr[:, 16:20] = addr[peer]
+        b.fill()
+        rows(b.buf)[:, 16:36] = torch.from_numpy(hdr).cuda()
+        rows(b.buf)[:, 16 + L:16 + P] = 0  # the padding as the route leaves it: both sends seal the same bytes
+        plain = b.buf.clone()
+        slots = torch.from_numpy(slot.view(np.int32).copy()).cuda()
+        d_peer_slot = torch.from_numpy(peer_slot.view(np.int32).copy()).cuda()
+        d_slot_peer = torch.from_numpy(slot_peer.view(np.int32).copy()).cuda()
+        unpadded = w.desc.copy()
+        unpadded["len"] = w.inner_len
+        desc_in = torch.from_numpy(unpadded.view(np.uint8).reshape(-1, 16)).cuda()
+        state0 = torch.from_numpy(np.tile(np.array([0, T, T], np.uint64), nk).view(np.int64)).cuda()
+        state = state0.clone()
+        now = torch.from_numpy(np.array([T + 5], np.uint64).view(np.int64)).cuda()
+        ws_send, ws_route, ws_recv = eng.send_workspace(n, nk), route.route_workspace(eng, n, nk), eng.replay_workspace(n, nk)
+        st_a = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        st_c = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        r_slots = torch.zeros(n, dtype=torch.int32, device="cuda")
+        r_desc = torch.zeros((n, 16), dtype=torch.uint8, device="cuda")
+        rx = torch.from_numpy(aead.rx_table(w.receivers, np.arange(nk, dtype=np.uint32))).cuda()
+        win = torch.zeros(nk * 33, dtype=torch.int64, device="cuda")
+        key = torch.zeros(n, dtype=torch.int32, device="cuda")
+        inner = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+        def gpu_ms(fn):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            z.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(z)
+
+        def wall_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def restore_send():
+            b.buf.copy_(plain)
+            state.copy_(state0)
+            torch.cuda.synchronize()
+
+        def resident():
+            eng.send_batch_dev_resident(b.keys, b.receivers, state, slots, b.desc_seal, b.buf, st_a, now_ns=now,
+                                        workspace=ws_send)
+
+        def routed():
+            route.send_batch_dev_routed(eng, b.keys, b.receivers, state, table, d_peer_slot, desc_in, b.buf, st_c,
+                                        now_ns=now, workspace=ws_route)
+
+        def route_only():
+            route.route_batch_dev(eng, table, d_peer_slot, desc_in, b.buf, r_slots, r_desc, st_c)
+
+        t = {k: [] for k in ("send_a_resident_gpu_ms", "send_a_resident_wall_ms", "send_c_routed_gpu_ms",
+                             "send_c_routed_wall_ms", "route_alone_gpu_ms", "recv_a_resident_gpu_ms",
+                             "recv_a_resident_wall_ms", "recv_c_checked_gpu_ms", "recv_c_checked_wall_ms",
+                             "check_alone_gpu_ms")}
+        frames = None
+        for rep in range(9):
+            restore_send()
+            t["send_a_resident_gpu_ms"].append(gpu_ms(resident))
+            frames_a = b.buf.clone()
+            restore_send()
+            t["send_c_routed_gpu_ms"].append(gpu_ms(routed))
+            assert (st_a == 0).all().item() and (st_c == 0).all().item(), "a send verdict is not OK"
+            assert torch.equal(b.buf, frames_a), "routed and resident sends sealed different frames"
+            frames = frames_a
+            restore_send()
+            t["send_a_resident_wall_ms"].append(wall_ms(resident))
+            restore_send()
+            t["send_c_routed_wall_ms"].append(wall_ms(routed))
+            restore_send()
+            t["route_alone_gpu_ms"].append(gpu_ms(route_only))
+            assert torch.equal(r_slots, slots)
+
+        def restore_recv():
+            b.buf.copy_(frames)
+            win.zero_()
+            torch.cuda.synchronize()
+
+        def recv():
+            eng.recv_batch_dev_resident(b.keys, rx, win, b.desc_open, b.buf, st_a, None, key, workspace=ws_recv)
+
+        def check():
+            route.route_check_batch_dev(eng, table, d_slot_peer, b.desc_open, key, b.buf, st_a, inner)
+
+        def checked():
+            recv()
+            check()
+
+        for rep in range(9):
+            restore_recv()
+            t["recv_a_resident_gpu_ms"].append(gpu_ms(recv))
+            assert (st_a == 0).all().item(), "a receive verdict is not OK"
+            t["check_alone_gpu_ms"].append(gpu_ms(check))
+            assert (st_a == 0).all().item() and (inner == L).all().item(), "the check turned a packet away"
+            restore_recv()
+            t["recv_c_checked_gpu_ms"].append(gpu_ms(checked))
+            restore_recv()
+            t["recv_a_resident_wall_ms"].append(wall_ms(recv))
+            restore_recv()
+            t["recv_c_checked_wall_ms"].append(wall_ms(checked))
+        r = {k: {"median": round(float(np.median(v[2:])), 4), "min": round(min(v[2:]), 4), "max": round(max(v[2:]), 4)}
+             for k, v in t.items()}
+        for side in ("send", "recv"):
+            a_, c_ = (k for k in t if k.startswith(side) and k.endswith("gpu_ms"))
+            r[f"{side}_c_over_a_gpu"] = round(r[c_]["median"] / r[a_]["median"], 3)
+            a_, c_ = (k for k in t if k.startswith(side) and k.endswith("wall_ms"))
+            r[f"{side}_c_over_a_wall"] = round(r[c_]["median"] / r[a_]["median"], 3)
+        return {"packets": n, "sessions": nk, "prefixes": NP, "table_words": int(table.numel()), **r}
+
+    res = {"cfg2": shape("cfg2"), "cfg4": shape("cfg4"),
+           "note": "9 alternating repetitions, the first two dropped (medians of seven, min-max); plaintext, state rows "
+                   "and windows restored outside the timed region; every figure by stream events (gpu_ms) or by host "
+                   "wall clock around the call and a device sync (wall_ms); (a) the unrouted resident call, (c) the "
+                   "routed send / the receive followed by the check, on the same frames in the same run; both sends "
+                   "sealed identical frames and every verdict was OK in every repetition"}
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "route_bench.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def _openssl_x25519(seconds=1.0):
     """OpenSSL's X25519 through libcrypto (ctypes releases the GIL, so threads run side by side): derivations
     per second on 1 and 16 threads, or None when the library is not there."""
@@ -620,11 +786,11 @@ def initiator_leg(eng):
 
 
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "handshake", "initiator"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
-                      ("replay", replay_leg), ("send", send_leg), ("handshake", handshake_leg),
+                      ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
                       ("initiator", initiator_leg)):
         if name in legs:
             out[name] = leg(eng)
