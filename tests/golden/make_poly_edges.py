@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/poly1305_edges.json: Poly1305 carry-edge vectors.
+"""Generate tests/golden/poly1305_edges.json and tests/golden/poly1305_flat_edges.json: Poly1305
+carry-edge vectors.
 
-Run by hand (deterministic from a fixed seed: two runs write the same bytes):
+Run by hand (deterministic from a fixed seed: two runs write the same bytes of both files):
 
     python tests/golden/make_poly_edges.py
 
@@ -40,6 +41,12 @@ acc_add instead gets "add_h4_in_masked" (entry h4 == 4 ignored), the rare half
 of that line.  The combine mutants (fold_drop_mask, combine_fold_removed) sit
 on a branch that random multi-segment packets do reach (two partial sums with
 h4 summing to 4 or more): RARE_MUTANTS lists the ones random data cannot see.
+
+The flattened kernel (rg_flat.hip) has a Poly1305 path of its own, modelled in the second half of this
+file: flat_pieces() (the deal of a one-packet call's chunks over the 64 lanes), Limbs.flat_tag() (the
+per-lane Horner pieces, the carry power, the 64-bit slot sums and phase F) and the second fixture,
+poly1305_flat_edges.json, made from a generator of its own seed after the first one (which therefore
+stays byte-identical).  See the comment above flat_pieces().
 """
 from __future__ import annotations
 
@@ -62,6 +69,8 @@ M128 = (1 << 128) - 1
 HI = 1 << 128
 SEED = 0x706F6C7931333035
 FIXTURE = os.path.join(HERE, "poly1305_edges.json")
+FLAT_FIXTURE = os.path.join(HERE, "poly1305_flat_edges.json")
+FLAT_SEED = 0x666C617431333035
 
 
 # ------------------------------------------------------------ integer reference
@@ -174,6 +183,73 @@ RARE_MUTANTS = ["mul_exit_drop_k", "add_h4_in_masked", "finish_fold_drop_mask", 
                 "finish_g4_drop_k", "fold_drop_k"]
 
 
+# ---- the flattened kernel's path (flat_pieces, Limbs.flat_tag): one mutant per decision point it adds.
+# Value edges that are no branch of the code (a piece or a carry that is 0 or p - 1 mod p, two pieces that
+# cancel, tag - s of 0 or 2^128 - 1) have no mutant of their own: a mutation that is wrong only there and
+# right mod p everywhere else does not exist.  Pieces and carries held at or above p get a "saturates"
+# mutant (the value is taken as p - 1), which stands for any code that assumes a canonical value.
+FLAT_MUTANTS = [
+    "flat_first_always_r",        # the first power step takes r although the top bit is clear
+    "flat_first_skipped",         # the 1-or-r first step is skipped (x stays 1, the top bit is lost)
+    "flat_pe1_as_zero",           # an exponent of 1 is taken for "no power"
+    "flat_select_sq_on_set",      # pow_step keeps the square where the bit is set
+    "flat_lead_zero_takes_mul",   # pow_step multiplies by r on a leading zero bit (x still 1)
+    "flat_zero_bit_takes_mul",    # pow_step multiplies by r on a clear bit below the top bit
+    "flat_skip_bit0",             # the power loop stops above bit 0
+    "flat_tend_one_chunk",        # the exponent of a lane with several chunks counts one chunk only
+    "flat_piece_ge_p_saturates",  # a carrying piece held at or above p is taken as p - 1
+    "flat_to26_l4_mask26",        # to26 cuts the top limb to 26 bits (h4 == 4 on entry)
+    "flat_cv_ge_p_saturates",     # a carry h r^pe held at or above p is taken as p - 1
+    "flat_walk_carry_1bit",       # phase F's limb walk keeps one bit of a slot's carry
+    "flat_walk_carry_5bit",       # ... five bits
+    "flat_fold_h4_and7",          # acc_fold sees h4 & 7
+    "flat_fold_h4_and63",         # acc_fold sees h4 & 63
+    "flat_open_borrow_chain_cut",  # tag - s: the borrow into the top word is dropped when all three below borrow
+]
+# of these and of MUTANTS, the ones 10^4 random one-packet messages do not see when run through flat_tag
+# (tests/test_poly_flat_edges_cpu.py checks both directions: these are never killed, the others are)
+FLAT_RARE_MUTANTS = ["flat_piece_ge_p_saturates", "flat_to26_l4_mask26", "flat_cv_ge_p_saturates", "fold_drop_k",
+                     "mul_exit_drop_k", "add_h4_in_masked", "finish_fold_drop_mask", "finish_use_g_0",
+                     "finish_g4_drop_k"]
+# Branches of the flat path that depend on r alone (r^(2^k), r^pe or the unselected x r of a power step held at
+# or above p or 2^130, the clamped-r product's own carries inside the chain): no data steers them, and a
+# counter search reaches 2^-30 at best against the 2^-98 or less they need.  Recorded with the "pow." prefix.
+FLAT_UNREACHABLE = ["pow.acc_sqr_gen:h>=p", "pow.to26:value>=p", "pow.to26:l4>=2^26",
+                    "pow.acc_mul:fold_carry_out_of_w3", "pow.acc_mul:exit_h4==4"]
+
+
+def flat_pieces(P: int) -> dict:
+    """The deal of a one-packet call's Poly1305 work over the 64 lanes of the flattened kernel
+    (rustyguard_amd/csrc/rg_flat.hip; P = payload bytes, a multiple of 16).
+
+    One packet is one unit and one sub-unit in all three flat modes.  launch_flat (rg_flat.hip:1123-1174): n = 1
+    gives head = 0, so no short-last-group split, and flat_coop_ok (:1115-1121) returns 0 below 4096 packets,
+    whatever rg_set_plan says (plan 0: balance = 0, plans 1 and 2: balance = 1, rg_batch.cpp launch_flat_any).
+    The one-wave search (:565-650) then has g = 0, f0 = 0, f1 = NU, gn = 1 for every unit u = j: the packet's
+    doubled midpoint is its work W (balance) or 1, the cuts are c(j) = [W < 2 floor(W j / NU)] for j > 0 and
+    c(0) = 0, c(NU) = 1 (:621-642), and unit j holds the packet when c(j) = 0 and c(j + 1) = 1: c rises with
+    j, so exactly one unit does, with m = 1 (:657-658), whatever the CU count.  Inside it (:730-740) D =
+    flat_chunks(nb) (:147), lane l takes chunks [l D >> 6, (l + 1) D >> 6) (:779), starts in packet 0 at chunk
+    c_lo (:782-787, kstart = 0) and ends in it (:924-929, kend = 0, rec.w = 0): pe = nb - 4 c_hi when blocks
+    remain behind the lane, pb = the top bit of the wave's largest pe (:934-938).  A lane carries (publishes
+    h r^pe, :951-983) when its cursor is still inside the packet after its last chunk (cur.t > 0: c_hi < D);
+    otherwise its piece holds the packet's last chunk and is published as it is (:279-281 open, :959-964 seal).
+
+    Returns nb, D, S (steps of the wave), pb and lanes: 64 dicts c_lo, c_hi, b0, b1 (data blocks [b0, b1)),
+    pe, carries."""
+    assert P % 16 == 0 and 0 <= P <= 1 << 20
+    nb = P >> 4
+    D = (nb + 3) >> 2 if nb else 1
+    lanes = []
+    for l in range(64):
+        c_lo, c_hi = (l * D) >> 6, ((l + 1) * D) >> 6
+        pe = nb - 4 * c_hi if c_hi > c_lo and 4 * c_hi < nb else 0
+        lanes.append({"c_lo": c_lo, "c_hi": c_hi, "b0": min(4 * c_lo, nb), "b1": min(4 * c_hi, nb), "pe": pe,
+                      "carries": c_hi > c_lo and c_hi < D})
+    mx = max(x["pe"] for x in lanes)
+    return {"nb": nb, "D": D, "S": (D + 63) // 64, "pb": mx.bit_length() - 1, "lanes": lanes}
+
+
 def words(x: int) -> list[int]:
     return [(x >> (32 * i)) & M32 for i in range(4)]
 
@@ -187,7 +263,7 @@ class Limbs:
     """rg_device.h's Poly1305 as written: an accumulator is [h0, h1, h2, h3, h4]."""
 
     def __init__(self, mutant: str | None = None):
-        assert mutant is None or mutant in MUTANTS
+        assert mutant is None or mutant in MUTANTS or mutant in FLAT_MUTANTS
         self.mut = mutant
         self.ev: set[str] = set()
         self.ctx = ""  # "pow." while a power of r is computed (not steerable)
@@ -315,6 +391,10 @@ class Limbs:
         l4 = ((h[3] >> 8) | (h[4] << 24)) & M32
         if l4 >= 1 << 26:
             self.hit("to26:l4>=2^26")
+            if not self.ctx:
+                self.hit("T:flat_to26_l4_mask26")
+                if self.mut == "flat_to26_l4_mask26":
+                    l4 &= M
         assert h[4] < 8 and l4 < 1 << 27  # the bounds stated in rg_device.h
         return [h[0] & M, ((h[0] >> 26) | (h[1] << 6)) & M, ((h[1] >> 20) | (h[2] << 12)) & M,
                 ((h[2] >> 14) | (h[3] << 18)) & M, l4]
@@ -480,6 +560,190 @@ class Limbs:
             afters.append(after)
         h = self.combine_pipe(parts, afters, r) if path[0] == "p" else self.combine_tile(parts, pws)
         return self.tail(h, r, s, 0, len(ct))
+
+    # ---- the flattened kernel (rg_flat.hip), a one-packet call: see flat_pieces()
+    def flat_pow(self, r, ln, pb):
+        """r^pe of a carrying lane as rg_flat.hip:973-978 and pow_step (:222-232) compute it: the first step is a
+        choice of 1 or r, every later one squares, multiplies by r and selects; pb is the wave's top bit"""
+        pe = ln["pe"]
+        multi = ln["c_hi"] - ln["c_lo"] >= 2
+        if multi:
+            self.ev.add("T:flat_tend_one_chunk")
+            if self.mut == "flat_tend_one_chunk":
+                pe = (pe + 4 * (ln["c_hi"] - ln["c_lo"] - 1)) & ((2 << pb) - 1)
+        one, rr = [1, 0, 0, 0, 0], [r[0], r[1], r[2], r[3], 0]
+        if pe == 1:
+            self.ev.add("flat:pow_pe==1")
+            self.ev.add("T:flat_pe1_as_zero")
+            if self.mut == "flat_pe1_as_zero":
+                return one
+        self.ctx = "pow."
+        bit = (pe >> pb) & 1
+        if bit:
+            self.ev.add("flat:pow_first_takes_r")
+            self.ev.add("T:flat_first_skipped")
+            if multi:
+                self.ev.add("flat:pow_top_bit_in_multi_chunk_lane")
+            px = one if self.mut == "flat_first_skipped" else rr
+        else:
+            self.ev.add("flat:pow_first_takes_1")
+            self.ev.add("T:flat_first_always_r")
+            px = rr if self.mut == "flat_first_always_r" else one
+        ones = 0  # steps that squared x = 1
+        for b in range(pb - 1, -1, -1):
+            if b == 0:
+                self.ev.add("T:flat_skip_bit0")
+                if self.mut == "flat_skip_bit0":
+                    break
+            lead = px == one
+            sq = list(px)
+            self.acc_sqr_gen(sq)
+            xr = list(sq)
+            self.acc_mul(xr, r)
+            if lead:
+                assert sq == one
+                ones += 1
+            if (pe >> b) & 1:
+                self.ev.add("flat:pow_bit_set")
+                self.ev.add("T:flat_select_sq_on_set")
+                px = sq if self.mut == "flat_select_sq_on_set" else xr
+            elif lead:
+                self.ev.add("T:flat_lead_zero_takes_mul")
+                px = xr if self.mut == "flat_lead_zero_takes_mul" else sq
+            else:
+                self.ev.add("flat:pow_bit_clear")
+                self.ev.add("T:flat_zero_bit_takes_mul")
+                px = xr if self.mut == "flat_zero_bit_takes_mul" else sq
+        if ones >= 2:
+            self.ev.add("flat:pow_squares_1_for>=2_steps")
+        self.ctx = ""
+        return px
+
+    def flat_sum(self, r, blocks):
+        """the packet's accumulator before the length block: per-lane Horner pieces, the carries h r^pe, the five
+        64-bit slot sums (add_h, :237-243), phase F's limb walk (:996-1005) and acc_fold (:1006)"""
+        L = flat_pieces(16 * len(blocks))
+        slots, vals = [0] * 5, []
+        for ln in L["lanes"]:
+            if ln["c_hi"] == ln["c_lo"]:
+                continue  # no chunk: nothing published (its power chain runs on x = 1 and is not used)
+            h, _ = self.horner(r, blocks[ln["b0"]:ln["b1"]])
+            if ln["carries"]:
+                v = self.value(h)
+                if v % P == 0:
+                    self.ev.add("flat:piece_h==0(mod p)")
+                if v >= P:
+                    self.ev.add("flat:piece_h>=p")
+                    self.ev.add("T:flat_piece_ge_p_saturates")
+                    if self.mut == "flat_piece_ge_p_saturates":
+                        h = words(P - 1) + [(P - 1) >> 128]
+                if h[4] == 4:
+                    self.ev.add("flat:piece_h4==4")
+                px = self.flat_pow(r, ln, L["pb"])
+                self.ctx = "pow."
+                G = self.make_gen(px)
+                self.ctx = ""
+                self.acc_mul_gen(h, G)
+                v = self.value(h)
+                if v % P <= 5:
+                    self.ev.add(f"flat:cv=={v % P}(mod p)")
+                if v % P == P - 1:
+                    self.ev.add("flat:cv==p-1(mod p)")
+                if v >= P:
+                    self.ev.add("flat:cv>=p")
+                    self.ev.add("T:flat_cv_ge_p_saturates")
+                    if self.mut == "flat_cv_ge_p_saturates":
+                        h = words(P - 1) + [(P - 1) >> 128]
+            vals.append(self.value(h))
+            for i in range(5):
+                slots[i] += h[i]
+        assert len(vals) <= 64 and max(slots) <= M64
+        if len(vals) == 2 and 0 < vals[0] < P and vals[0] + vals[1] == P:
+            self.ev.add("flat:two_pieces_cancel")
+        # phase F: carry the slot sums into 32-bit limbs
+        h, t = [0] * 5, 0
+        for i in range(4):
+            k = t >> 32
+            if i:
+                if k >= 2:
+                    self.ev.add("flat:slot_carry>=2")
+                    self.ev.add("T:flat_walk_carry_1bit")
+                    if self.mut == "flat_walk_carry_1bit":
+                        k &= 1
+                if k >= 32:
+                    self.ev.add("flat:slot_carry>=32")
+                    self.ev.add("T:flat_walk_carry_5bit")
+                    if self.mut == "flat_walk_carry_5bit":
+                        k &= 31
+            t = (k + slots[i]) & M64
+            h[i] = t & M32
+        k = t >> 32
+        if k >= 2:
+            self.ev.add("flat:slot_carry>=2")
+            self.ev.add("T:flat_walk_carry_1bit")
+            if self.mut == "flat_walk_carry_1bit":
+                k &= 1
+        if k >= 32:
+            self.ev.add("flat:slot_carry>=32")
+            self.ev.add("T:flat_walk_carry_5bit")
+            if self.mut == "flat_walk_carry_5bit":
+                k &= 31
+        h[4] = (k + slots[4]) & M32
+        if self.value(h) % P == 0 and self.value(h) > 0:
+            self.ev.add("flat:sum==0(mod p)")
+            if self.value(h) == P:
+                self.ev.add("flat:sum_limbs==p")
+        if h[4] >= 8:
+            self.ev.add("flat:h4>=8")
+            self.ev.add("T:flat_fold_h4_and7")
+            if self.mut == "flat_fold_h4_and7":
+                h[4] &= 7
+        if h[4] >= 64:
+            self.ev.add("flat:h4>=64")
+            self.ev.add("T:flat_fold_h4_and63")
+            if self.mut == "flat_fold_h4_and63":
+                h[4] &= 63
+        if (self.value(h) & M128) + 5 * (h[4] >> 2) > M128:
+            self.ev.add("flat:fold_carry_out_of_h3" + ("_h4>=8" if h[4] >= 8 else ""))
+        self.acc_fold(h)
+        return h
+
+    def flat_tag(self, otk: bytes, ct: bytes, direction: str = "seal", tag: bytes | None = None):
+        """A one-packet call of the flattened kernel on ciphertext ct (whole blocks).  "seal": the tag (acc_finish
+        adds s, :1014).  "open": whether `tag` is accepted: phase A holds tag - s mod 2^128 (:846-852), phase F
+        finishes with s = 0 and compares (:1019-1021)."""
+        assert len(ct) % 16 == 0 and direction in ("seal", "open")
+        k = [int.from_bytes(otk[4 * i:4 * i + 4], "little") for i in range(8)]
+        r, s = self.make_mul(k[:4]), k[4:]
+        h = self.flat_sum(r, to_blocks(ct))
+        self.acc_add(h, [0, 0, len(ct), 0], 1)
+        self.acc_mul(h, r)
+        v = self.value(h)
+        if P <= v < 1 << 130:
+            self.ev.add(f"flat:finish_held_p+{v - P}")
+        elif v >= 1 << 130:
+            self.ev.add(f"flat:finish_held_2^130+{v - (1 << 130)}" if v - (1 << 130) < 2 else "flat:finish_held_>2^130+1")
+        if direction == "seal":
+            return self.acc_finish(h, s)
+        t = [int.from_bytes(tag[4 * i:4 * i + 4], "little") for i in range(4)]
+        sw, b, borrows = [0] * 4, 0, []
+        for i in range(4):
+            if i == 3 and borrows == [1, 1, 1]:
+                self.ev.add("T:flat_open_borrow_chain_cut")
+                if self.mut == "flat_open_borrow_chain_cut":
+                    b = 0
+            d = t[i] - s[i] - b
+            b = int(d < 0)
+            borrows.append(b)
+            sw[i] = d & M32
+        if all(borrows):
+            self.ev.add("flat:open_tag-s_borrows_every_word")
+        x = sw[0] | sw[1] << 32 | sw[2] << 64 | sw[3] << 96
+        if x == 0:
+            self.ev.add("flat:open_tag-s==0")
+        if x == M128:
+            self.ev.add("flat:open_tag-s==2^128-1")
+        return self.acc_finish(h, [0, 0, 0, 0]) == x.to_bytes(16, "little")
 
 
 SEG_PATHS = {2: ["p2", "t2"], 4: ["p4", "t4"]}
@@ -766,6 +1030,212 @@ def generate() -> dict:
             "vectors": g.vectors}
 
 
+# ------------------------------------------------- the flat kernel's own fixture
+def flat_vector_ct(v) -> bytes:
+    """the ciphertext of a flat vector: filler bytes from its seed, the solved blocks put over them"""
+    ct = bytearray(random.Random(v["seed"]).randbytes(v["P"]))
+    for i, hx in v["solved"]:
+        ct[16 * i:16 * i + 16] = bytes.fromhex(hx)
+    return bytes(ct)
+
+
+def flat_vector_otk(v) -> bytes:
+    return one_time_key(bytes.fromhex(v["key"]), oracle.wg_nonce(v["counter"]))
+
+
+def flat_model(v, mutant=None, ct=None):
+    """a flat vector under the model, both directions: {"seal": (events, tag), "open": (events, accepted)}"""
+    otk, ct = flat_vector_otk(v), flat_vector_ct(v) if ct is None else ct
+    out = {}
+    for d in ("seal", "open"):
+        m = Limbs(mutant)
+        res = m.flat_tag(otk, ct, d, bytes.fromhex(v["tag"]))
+        out[d] = (sorted(m.ev), res)
+    return out
+
+
+def flat_frame(v, pad=(48, 80), fill_seed=5):
+    """The vector as a one-packet call over the include/rg_aead.h buffer contract: random bytes, the frame
+    [header 16][ciphertext][tag 16] at offset pad[0], pad[1] random bytes behind it.  Returns a dict as
+    frame_batch does (plain: the buffer opened by the C oracle)."""
+    import numpy as np
+
+    rng = np.random.default_rng(fill_seed + v["id"])
+    ct, P_ = flat_vector_ct(v), v["P"]
+    keys = np.frombuffer(bytes.fromhex(v["key"]), np.uint8).reshape(1, 32).copy()
+    counters = np.array([v["counter"]], np.uint64)
+    receivers = rng.integers(1, 2**32, 1, dtype=np.uint64).astype(np.uint32)
+    desc = np.zeros(1, oracle.DESC_DTYPE)
+    desc["offset"], desc["len"], desc["key_idx"] = pad[0], P_, 0
+    buf = rng.integers(0, 256, pad[0] + P_ + 32 + pad[1], dtype=np.uint8)
+    frame = b"".join([(4).to_bytes(4, "little"), int(receivers[0]).to_bytes(4, "little"),
+                      v["counter"].to_bytes(8, "little"), ct, bytes.fromhex(v["tag"])])
+    buf[pad[0]:pad[0] + len(frame)] = np.frombuffer(frame, np.uint8)
+    od = desc.copy()
+    od["len"] += 32
+    plain = buf.copy()
+    st, ctr = oracle.open_batch(keys, od, plain)
+    assert (st == 0).all() and np.array_equal(ctr, counters)
+    return {"keys": keys, "receivers": receivers, "counters": counters, "desc_seal": desc, "desc_open": od,
+            "sealed": buf, "plain": plain, "at": pad[0], "P": P_}
+
+
+class FlatGen:
+    def __init__(self):
+        self.rng = random.Random(FLAT_SEED)
+        self.vectors = []
+        self.tries = []
+
+    def vector(self, label, P_, steps, want=()):
+        """steps: [(lane, what, T)] with what = "h" (the lane's Horner piece from zero), "cv" (h r^pe, the value
+        the lane publishes), "pre" (the packet's sum before the length block) or "final" (the state acc_finish
+        gets), T an integer or f(r, s).  The free block is the first block of the lane's piece; a retry redraws
+        the piece's second block (recorded with the solved ones), or, where the piece has one block, the
+        counter.  "pre" and "final" come last and use a lane no other step uses.  want: events the model must
+        record in both directions ("open:" in front: in the open alone)."""
+        rng, L = self.rng, flat_pieces(P_)
+        nb = L["nb"]
+        key = rng.randbytes(32)
+        for t0 in range(256):
+            ctr = rng.getrandbits(rng.choice([8, 32, 48, 62]))
+            otk = one_time_key(key, oracle.wg_nonce(ctr))
+            r, s = clamp(int.from_bytes(otk[:16], "little")), int.from_bytes(otk[16:32], "little")
+            seed = rng.getrandbits(32)
+            blocks = to_blocks(random.Random(seed).randbytes(P_)) + [P_ << 64]
+            solved = {}
+            for lane, what, T in steps:
+                ln = L["lanes"][lane]
+                b0, b1, pe = ln["b0"], ln["b1"], ln["pe"]
+                assert b1 > b0 and b0 not in solved
+                F = {"h": lambda b: ref_state(r, b[b0:b1]),
+                     "cv": lambda b: ref_state(r, b[b0:b1]) * pow(r, pe, P) % P,
+                     "pre": lambda b: ref_state(r, b[:nb]),
+                     "final": lambda b: ref_state(r, b)}[what]
+                target = (T(r, s) if callable(T) else T) % P
+                x = None
+                for t1 in range(64):
+                    x = solve_block(F, blocks, b0, target)
+                    if x is not None or b1 - b0 < 2:
+                        break
+                    blocks[b0 + 1] = solved[b0 + 1] = rng.getrandbits(128)
+                if x is None:
+                    break
+                blocks[b0] = solved[b0] = x
+                assert F(blocks) == target
+            else:
+                self.tries.append(t0 + 1)
+                return self.emit(label, P_, key, ctr, seed, solved, blocks[:nb], want)
+        raise RuntimeError(f"target not met: {label}")
+
+    def emit(self, label, P_, key, ctr, seed, solved, blocks, want):
+        ct = b"".join(b.to_bytes(16, "little") for b in blocks)
+        v = {"id": len(self.vectors), "label": label, "P": P_, "key": key.hex(), "counter": ctr, "seed": seed,
+             "solved": [[i, solved[i].to_bytes(16, "little").hex()] for i in sorted(solved)]}
+        assert flat_vector_ct(v) == ct
+        tag = ref_tag(flat_vector_otk(v), mac_input(b"", ct))
+        v["tag"] = tag.hex()
+        res = flat_model(v, ct=ct)
+        assert res["seal"][1] == tag and res["open"][1] is True, label
+        ev = {d: {e for e in res[d][0] if not e.startswith("T:")} for d in res}
+        for w in want:
+            assert (w[5:] in ev["open"]) if w.startswith("open:") else (w in ev["seal"] and w in ev["open"]), (label, w)
+        v["events"] = sorted(ev["seal"] & ev["open"])
+        v["events_seal"] = sorted(ev["seal"] - ev["open"])
+        v["events_open"] = sorted(ev["open"] - ev["seal"])
+        self.vectors.append(v)
+        return v
+
+
+def flat_old_fixture_finish(vectors) -> dict:
+    """The acc_finish branches that the batch vectors of poly1305_edges.json take in straight Horner order ("h")
+    and as one-packet calls of the flat kernel ("flat"), by branch name -> number of vectors: the flat
+    kernel's state before acc_finish is another representative of the same value mod p."""
+    out = {"h": {}, "flat": {}}
+    for v in vectors:
+        if v["kind"] != "batch":
+            continue
+        otk, ct = vector_otk(v), bytes.fromhex(v["ct"])
+        a, b = Limbs(), Limbs()
+        assert a.tag(otk, b"", ct, "h") == b.flat_tag(otk, ct) == bytes.fromhex(v["tag"])
+        for name, m in (("h", a), ("flat", b)):
+            for e in m.ev:
+                if e.startswith("acc_finish:"):
+                    out[name][e] = out[name].get(e, 0) + 1
+    return out
+
+
+def generate_flat() -> dict:
+    g = FlatGen()
+    c = lambda v: (lambda r, s: v)  # noqa: E731
+    small = [(str(t), t) for t in range(7)] + [("p-1", P - 1)]
+    # ---- P = 128: two 4-block pieces (lanes 31 and 63), pe = 4: r, then two squarings
+    for name, t in small:
+        want = ["flat:piece_h>=p"] if t < 5 else ["flat:piece_h4==4", "to26:l4>=2^26"] if t < 7 else []
+        g.vector(f"P=128: carrying piece h = {name}", 128, [(31, "h", t)], want + (["flat:piece_h==0(mod p)"] if t == 0 else []))
+    for name, t in small[:6] + small[7:]:
+        g.vector(f"P=128: carry h r^4 = {name}", 128, [(31, "cv", t)], [f"flat:cv=={name}(mod p)"])
+    x = g.rng.getrandbits(129)
+    g.vector("P=128: carry = x, last piece = p - x (the sum's limbs are exactly p)", 128,
+             [(31, "cv", x), (63, "h", P - x)], ["flat:two_pieces_cancel", "flat:sum_limbs==p", "flat:sum==0(mod p)"])
+    # ---- P = 80: a 4-block piece with pe = 1 and a 1-block piece
+    g.vector("P=80: carrying piece h = 0, pe = 1", 80, [(31, "h", 0)], ["flat:pow_pe==1", "flat:piece_h==0(mod p)"])
+    g.vector("P=80: carry h r = p-1", 80, [(31, "cv", P - 1)], ["flat:pow_pe==1", "flat:cv==p-1(mod p)"])
+    g.vector("P=80: carry h r = 5 (h4 == 4 into the slots)", 80, [(31, "cv", 5)], ["flat:cv==5(mod p)"])
+    g.vector("P=80: carry = 4, last piece = 4 (both held as 2^130 - 1)", 80, [(31, "cv", 4), (63, "h", 4)],
+             ["flat:cv>=p"])
+    # ---- the final state and the open's compare, through every layout
+    fin = [(f"{t} (held as p+{t})", c(t), [f"flat:finish_held_p+{t}", "acc_finish:use_g"]) for t in range(5)]
+    fin += [("5 (held as 2^130)", c(5), ["flat:finish_held_2^130+0", "acc_finish:fold_h4>=4"]),
+            ("6 (held as 2^130+1)", c(6), ["flat:finish_held_2^130+1", "acc_finish:fold_h4>=4"]),
+            ("p-1", c(P - 1), []),
+            ("low words fffffffb,ff..,ff.. (h + 5 carries through three words)",
+             c((1 << 96) - 5 | 0x12345678 << 96 | 2 << 128), []),
+            ("tag = s (tag - s = 0)", c(0), ["open:flat:open_tag-s==0"]),
+            ("2^128-1 (tag - s = 2^128 - 1)", c(M128), ["open:flat:open_tag-s==2^128-1"]),
+            ("tag = 1 (T + s carries, tag - s borrows through every word)", lambda r, s: ((-s) & M128) + 1,
+             ["open:flat:open_tag-s_borrows_every_word"])]
+    sizes = [80, 128, 1504, 4096, 4112, 8208]
+    for i, (name, T, want) in enumerate(fin):
+        for P_ in (sizes[i % 6], sizes[(i + 3) % 6]):
+            lanes = [l for l, ln in enumerate(flat_pieces(P_)["lanes"]) if ln["b1"] - ln["b0"] >= 2]
+            g.vector(f"P={P_}: final state = {name}", P_, [(lanes[g.rng.randrange(len(lanes))], "final", T)], want)
+    # ---- P = 1504 (24 pieces, exponents 90 .. 2, a 2-block last chunk)
+    live = [l for l, ln in enumerate(flat_pieces(1504)["lanes"]) if ln["c_hi"] > ln["c_lo"]]
+    assert len(live) == 24
+    for name, t in (("0", 0), ("3", 3), ("5", 5), ("p-1", P - 1)):
+        g.vector(f"P=1504: first lane's piece h = {name}, last carrying lane's carry h r^2 = {name}", 1504,
+                 [(live[0], "h", t), (live[-2], "cv", t)],
+                 ["flat:pow_squares_1_for>=2_steps", "flat:pow_first_takes_1", "flat:pow_first_takes_r"])
+    g.vector("P=1504: sum of the 24 pieces = 0", 1504, [(live[11], "pre", 0)], ["flat:sum==0(mod p)", "flat:h4>=8"])
+    g.vector("P=1504: every piece = p-1", 1504, [(l, "cv", P - 1) for l in live], ["flat:slot_carry>=2", "flat:h4>=64"])
+    # ---- P = 4096: 64 pieces of one chunk
+    g.vector("P=4096: every piece = p-1 (the largest slot sums and h4)", 4096, [(l, "cv", P - 1) for l in range(64)],
+             ["flat:slot_carry>=32", "flat:h4>=64", "flat:cv==p-1(mod p)"])
+    g.vector("P=4096: 63 pieces = p-1, the last = 377 (the fold of the large h4 carries out of h3)", 4096,
+             [(l, "cv", P - 1) for l in range(63)] + [(63, "h", 377)], ["flat:fold_carry_out_of_h3_h4>=8"])
+    g.vector("P=4096: every carry = 0 (held as p), last piece = 0", 4096, [(l, "cv", 0) for l in range(64)],
+             ["flat:cv==0(mod p)", "flat:sum==0(mod p)"])
+    g.vector("P=4096: every carrying piece h = 6 (held as 2^130 + 1)", 4096, [(l, "h", 6) for l in range(63)],
+             ["flat:piece_h4==4"])
+    # ---- P = 4112: lane 63 holds two chunks (the second of one block)
+    g.vector("P=4112: the two-chunk last piece = p-1, lane 62's carry h r^5 = p-1", 4112,
+             [(62, "cv", P - 1), (63, "h", P - 1)], ["flat:cv==p-1(mod p)"])
+    g.vector("P=4112: sum of the 64 pieces = 0", 4112, [(63, "pre", 0)], ["flat:sum==0(mod p)"])
+    # ---- P = 8208: two and three chunks per lane, 9-bit exponents
+    for name, t in (("0", 0), ("4", 4), ("6", 6), ("p-1", P - 1)):
+        g.vector(f"P=8208: lane 0's piece (two chunks, the top exponent bit) h = {name}; lane 31's carry (three "
+                 f"chunks) = {name}", 8208, [(0, "h", t), (31, "cv", t)], ["flat:pow_top_bit_in_multi_chunk_lane"])
+    g.vector("P=8208: every piece = p-1", 8208, [(l, "cv", P - 1) for l in range(64)], ["flat:slot_carry>=32"])
+    # ---- P = 65536: 16 chunks a lane, 12-bit exponents
+    g.vector("P=65536: every piece = p-1", 65536, [(l, "cv", P - 1) for l in range(64)], ["flat:h4>=64"])
+    g.vector("P=65536: lane 0's piece h = 0, lane 62's carry = 5, final state = 0 (held as p+0)", 65536,
+             [(0, "h", 0), (62, "cv", 5), (40, "final", 0)], ["flat:finish_held_p+0", "flat:piece_h==0(mod p)"])
+    return {"generator": "tests/golden/make_poly_edges.py", "seed": FLAT_SEED, "p": "2^130-5",
+            "unreachable": FLAT_UNREACHABLE,
+            "solver_tries": {"mean": round(sum(g.tries) / len(g.tries), 2), "max": max(g.tries)},
+            "vectors": g.vectors}
+
+
 def dumps(data) -> str:
     return json.dumps(data, indent=0, separators=(",", ":")) + "\n"
 
@@ -777,6 +1247,13 @@ def main():
         f.write(dumps(data))
     print("wrote", FIXTURE, os.path.getsize(FIXTURE), "bytes,", len(data["vectors"]), "vectors, solver tries",
           data["solver_tries"])
+    flat = generate_flat()
+    with open(FLAT_FIXTURE, "w") as f:
+        f.write(dumps(flat))
+    print("wrote", FLAT_FIXTURE, os.path.getsize(FLAT_FIXTURE), "bytes,", len(flat["vectors"]), "vectors, solver tries",
+          flat["solver_tries"])
+    print("acc_finish branches of the first fixture's batch vectors, straight and through the flat path:",
+          flat_old_fixture_finish(data["vectors"]))
 
 
 if __name__ == "__main__":

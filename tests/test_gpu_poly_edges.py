@@ -6,6 +6,9 @@ less; the fixture's vectors sit on them (tests/golden/make_poly_edges.py: accumu
 cancel or whose fold carries).  Every kernel family opens them, rejects them with one tag bit flipped and
 seals their plaintexts back, bit for bit against the fixture, which tests/test_poly_edges_cpu.py pins to
 Poly1305 in Python integers and to the C oracle.
+
+The flattened kernel's own path (per-lane pieces, carry powers, 64-bit slot sums, phase F) gets a fixture of its
+own, tests/golden/poly1305_flat_edges.json, sent one packet per call: tests/test_poly_flat_edges_cpu.py.
 """
 import sys
 
@@ -71,6 +74,50 @@ def test_batched_edge_vectors(engine, mode):
                 assert got[o + 16: o + 16 + p].tobytes().hex() == v["ct"], v["label"]
                 assert got[o + 16 + p: o + 32 + p].tobytes().hex() == v["tag"], v["label"]
             assert np.array_equal(got, b["sealed"])
+    finally:
+        _reset(engine)
+
+
+FLAT_VECTORS = load_golden("poly1305_flat_edges.json")["vectors"]
+_flat_frames = {}
+
+
+def _flat_frame(v):
+    """the vector as a one-packet call (built once, shared by the three modes, never written to)"""
+    if v["id"] not in _flat_frames:
+        _flat_frames[v["id"]] = G.flat_frame(v)
+    return _flat_frames[v["id"]]
+
+
+@pytest.mark.parametrize("mode", [m for m in MODES if m[0] == "flat"], ids=_mode_id)
+def test_flat_one_packet_edge_vectors(engine, mode):
+    """tests/golden/poly1305_flat_edges.json: each vector alone in a call, so that the flattened kernel deals its
+    chunks over the lanes as make_poly_edges.flat_pieces says and the vector's pieces, carry powers and slot sums
+    are the ones it was solved for.  Open, open with the tag's lowest and highest bit flipped (the frame comes
+    back as it was), seal: bit for bit, in the three flat modes."""
+    _configure(engine, mode)
+    try:
+        for v in FLAT_VECTORS:
+            b = _flat_frame(v)
+            at, n = b["at"], b["P"]
+            back, st, co = _gpu_open(engine, b["keys"], b["desc_open"], b["sealed"])
+            assert engine.last_kernel() == 3
+            assert st[0] == aead.PKT_OK, v["label"]
+            assert co[0] == v["counter"], v["label"]
+            assert np.array_equal(back, b["plain"]), v["label"]
+            for byte, bit in ((-16, 0x01), (-1, 0x80)):
+                forged = b["sealed"].copy()
+                forged[at + n + 32 + byte] ^= bit
+                back, st, _ = _gpu_open(engine, b["keys"], b["desc_open"], forged)
+                assert engine.last_kernel() == 3
+                assert st[0] == aead.PKT_DECRYPT_ERR, v["label"]
+                assert np.array_equal(back, forged), v["label"]
+            got, st = _gpu_seal(engine, b["keys"], b["receivers"], b["desc_seal"], b["counters"], b["plain"])
+            assert engine.last_kernel() == 3
+            assert st[0] == aead.PKT_OK, v["label"]
+            assert got[at + 16 + n: at + 32 + n].tobytes().hex() == v["tag"], v["label"]
+            assert got[at + 16: at + 16 + n].tobytes() == G.flat_vector_ct(v), v["label"]
+            assert np.array_equal(got, b["sealed"]), v["label"]  # header, and every byte outside the frame
     finally:
         _reset(engine)
 
