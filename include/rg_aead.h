@@ -308,8 +308,8 @@ int64_t rg_peer_table_find(const rg_hs_peer *peers, const uint32_t *table, uint3
  * mac1 and mac2 are NOT checked here: run the filter first.  The row of every message whose status is not
  * RG_PKT_OK is written as 128 zero bytes with peer = RG_PEER_NONE, so no partial secret state is left
  * behind; a lane stores its status after its row.  The timestamp-replay check (peer.latest_ts,
- * handshake.rs:88-91) is an in-order pass per peer and stays with the caller, which reads results[i].
- * timestamp and .peer before it lets a row on to the response (clear its gate byte otherwise).
+ * handshake.rs:88-91) is an in-order pass per peer: rg_peer_ts_batch_dev (below) runs it on this call's
+ * results and status on the same stream, before they go on to the response.
  * RG_EINVAL also for cap not a power of two; own, peers, desc and results must be 16-byte aligned,
  * peer_table 4-byte aligned. */
 int rg_handshake_init_batch_dev(rg_ctx *ctx, const rg_hs_static *own, const rg_hs_peer *peers, uint32_t npeers,
@@ -434,6 +434,110 @@ int rg_handshake_finish_batch_dev(rg_ctx *ctx, const rg_hs_static *own, const rg
                                   uint8_t *transport_keys /* [n][64]: send key || receive key */,
                                   uint32_t *pend_idx_out /* [n] */, uint32_t *remote_out /* [n] */,
                                   uint32_t *claim /* [npending] workspace */, uint8_t *status, void *stream);
+
+/* ------------------------------ per-peer handshake state on the device (batch, async) */
+/* The three fields the reference keeps per peer around a handshake (Peer, rustyguard-core/src/lib.rs:170-180) as
+ * a device table, one row per row of rg_hs_peer, so that the responder chain and the initiator's cookie loop run
+ * on one stream with no host step and can be captured into a graph.  A zeroed row is Peer::new.  The caller owns
+ * the table; the library reads and writes only the rows a batch names.  Cookies are never expired here, as in
+ * the reference (WireGuard's 120 s rule is the caller's: clear has_cookie).
+ *
+ * The conventions are the handshake calls': all pointers are device memory; the calls enqueue on `stream` and
+ * return without waiting and keep nothing in the context; n == 0 returns RG_OK; RG_EINVAL with nothing enqueued
+ * for a null required pointer (state, cookie_keys and claim are required when npeers > 0), n > 2^32 - 1, a
+ * misaligned array or a short workspace.  state and struct rows must be 16-byte aligned, word arrays (peers_out,
+ * peer_idx, cookies_out, claim, sess_table) 4-byte aligned.  A lane stores its status after everything else
+ * it writes.
+ *
+ * The chains, each on one stream (the existing calls take the new arrays as they are):
+ *   responder: rg_cookie_reply_batch_dev -> rg_handshake_init_batch_dev (gate = the filter's status) ->
+ *     rg_peer_ts_batch_dev -> rg_peer_cookies_batch_dev (peers_out) -> rg_handshake_resp_batch_dev (gate = status)
+ *     -> rg_peer_mac1_batch_dev (peers_out, responses, 96, 60)
+ *   initiator: rg_peer_cookies_batch_dev (peer_idx) -> rg_handshake_initiate_batch_dev -> rg_peer_mac1_batch_dev
+ *     (peer_idx, messages, 160, 116); later, on the incoming type-3 messages, rg_peer_cookie_consume_batch_dev
+ *     (gate = the status of whatever admission filter the caller runs, or NULL: a CookieMessage carries no mac). */
+typedef struct rg_hs_peer_state {    /* 64 bytes, 16-byte aligned rows */
+    uint8_t latest_ts[12];           /* peer.latest_ts: the newest TAI64N an initiation of this peer carried */
+    uint32_t has_cookie;             /* 0 or 1: peer.cookie is Some */
+    uint8_t cookie[16];              /* peer.cookie */
+    uint8_t last_sent_mac1[16];      /* peer.last_sent_mac1: the AAD of a cookie reply to what we sent last */
+    uint8_t pad[16];
+} rg_hs_peer_state;
+
+/* rg_peer_ts_batch_dev: the timestamp-replay check of handle_handshake_init (handshake.rs:88-91) for the rows
+ * rg_handshake_init_batch_dev just wrote, in place.  A row is eligible iff status[i] == RG_PKT_OK and
+ * results[i].peer < npeers.  The outcome equals, bit for bit, this loop over the eligible rows in array order:
+ *     if results[i].timestamp < state[p].latest_ts (as bytes, i.e. big-endian)   RG_PKT_REJECTED
+ *     else state[p].latest_ts = results[i].timestamp                             stays RG_PKT_OK
+ * An equal timestamp passes (the reference compares with <).  Every other row:
+ *   status[i] != RG_PKT_OK                            keeps its status
+ *   RG_PKT_OK with results[i].peer >= npeers          RG_PKT_INVALID
+ * A row this call turns down (rejected or invalid) has its results row wiped to 128 zero bytes with peer =
+ * RG_PEER_NONE, as the init call does for its own failures.  peers_out[i] is the peer of a row that is RG_PKT_OK
+ * afterwards and RG_PEER_NONE otherwise: the peer_idx of rg_peer_cookies_batch_dev and rg_peer_mac1_batch_dev.
+ *
+ * No ordering by arrival: whether or not a row is accepted, latest after it is max(latest, its timestamp), so
+ * row i is accepted iff its timestamp >= max(state[p].latest_ts, the timestamps of the eligible rows j < i of
+ * peer p) -- a segmented exclusive prefix maximum over the rows grouped stably by peer (the core the device
+ * anti-replay commit and the send reservation share), with the 96-bit timestamp as the value -- and the peer's
+ * last row leaves max(latest_ts, the group's maximum) in the table.  A peer with no eligible row keeps its row
+ * byte for byte.
+ *
+ * workspace: rg_peer_ts_workspace_size(n, npeers) bytes, 16-byte aligned, the call's scratch (0 when n is too
+ * large for any workspace; non-decreasing in n and in npeers). */
+size_t rg_peer_ts_workspace_size(size_t n, uint32_t npeers);
+int rg_peer_ts_batch_dev(rg_ctx *ctx, rg_hs_peer_state *state, uint32_t npeers,
+                         rg_hs_init_result *results /* [n], written */, uint8_t *status /* [n], in place */,
+                         uint32_t *peers_out /* [n] */, size_t n, void *workspace, size_t workspace_len,
+                         void *stream);
+
+/* rg_peer_cookie_consume_batch_dev: Sessions::handle_cookie / decrypt_cookie (handshake.rs:233-257,
+ * rustyguard-crypto/src/lib.rs) for n CookieMessages.  sess_table maps a receiver id (the session id of an
+ * initiation or response we sent) to its peer row: an rg_rx_table_build table.  cookie_keys[p] is
+ * cookie_key(peers[p].public_key) = BLAKE2s-256("cookie--" || public key) (lib.rs:75-77).  desc[i]: offset, len
+ * = whole message.  Per message, in this order:
+ *   offset % 16 != 0                                   RG_PKT_UNALIGNED
+ *   frame outside [buf, buf + buf_len), or len != 64   RG_PKT_INVALID
+ *   gate && gate[i] != RG_PKT_OK, or
+ *   key_idx == RG_KEY_SKIP                             RG_PKT_REJECTED, message not read
+ *   type word != 3                                     RG_PKT_INVALID
+ *   msg[4..8] not in sess_table                        RG_PKT_REJECTED
+ *   its peer >= npeers                                 RG_PKT_INVALID
+ *   XChaCha20-Poly1305 open fails                      RG_PKT_DECRYPT_ERR
+ *   otherwise                                          RG_PKT_OK, cookies_out[i] = the cookie
+ * The open: key cookie_keys[p], nonce msg[8..32], AAD state[p].last_sent_mac1 as it stood before the call,
+ * ciphertext msg[32..48], tag msg[48..64]; the tag comparison has no early exit.  On any failure cookies_out[i]
+ * is zero.  buf is never written (the reference decrypts in place).
+ *
+ * Every message that opens is RG_PKT_OK, as in the reference, where a later valid cookie overwrites an earlier
+ * one; the one that stays in state[p].cookie is that of the highest message index, whatever order the lanes
+ * arrive in: the call zeroes claim[npeers] (a workspace of the call), every message that opened takes
+ * atomicMax(&claim[p], i + 1), and a commit launch over the peers copies cookies_out[claim[p] - 1] into the row
+ * and sets has_cookie = 1.  A peer with no valid message keeps its row byte for byte.  The call writes only
+ * cookie and has_cookie and reads only last_sent_mac1.
+ * RG_EINVAL also for sess_cap not a power of two; cookie_keys and desc must be 16-byte aligned. */
+int rg_peer_cookie_consume_batch_dev(rg_ctx *ctx, rg_hs_peer_state *state, uint32_t npeers,
+                                     const uint8_t *cookie_keys /* [npeers][32] */, const rg_rx_entry *sess_table,
+                                     uint32_t sess_cap, const rg_pkt_desc *desc, const uint8_t *gate /* [n] or NULL */,
+                                     size_t n, const uint8_t *buf, size_t buf_len, uint8_t *cookies_out /* [n][16] */,
+                                     uint32_t *claim /* [npeers] workspace */, uint8_t *status, void *stream);
+
+/* rg_peer_cookies_batch_dev: the cookies / has_cookie arrays rg_handshake_initiate_batch_dev and
+ * rg_handshake_resp_batch_dev take, out of the table: cookies_out[i] = state[p].cookie and has_cookie_out[i] = 1
+ * for p = peer_idx[i] < npeers with has_cookie set; 16 zero bytes and 0 for every other row (RG_PEER_NONE
+ * included). */
+int rg_peer_cookies_batch_dev(rg_ctx *ctx, const rg_hs_peer_state *state, uint32_t npeers,
+                              const uint32_t *peer_idx /* [n] */, size_t n, uint8_t *cookies_out /* [n][16] */,
+                              uint8_t *has_cookie_out /* [n] */, void *stream);
+
+/* rg_peer_mac1_batch_dev: peer.last_sent_mac1 after a send (handshake.rs:108, new_handshake).  For every row with
+ * status[i] == RG_PKT_OK and p = peer_idx[i] < npeers: state[p].last_sent_mac1 = the 16 bytes at messages +
+ * i * stride + mac1_offset; of several rows of one peer the highest i stays (the in-order result), by atomicMax
+ * into claim[npeers] (zeroed by the call) and a commit launch over the peers.  The initiator passes (160, 116),
+ * the responder (96, 60).  RG_EINVAL unless mac1_offset % 4 == 0 and mac1_offset + 16 <= stride. */
+int rg_peer_mac1_batch_dev(rg_ctx *ctx, rg_hs_peer_state *state, uint32_t npeers, const uint32_t *peer_idx /* [n] */,
+                           const uint8_t *status /* [n] */, const uint8_t *messages, uint32_t stride,
+                           uint32_t mac1_offset, size_t n, uint32_t *claim /* [npeers] workspace */, void *stream);
 
 /* Tuning knobs.  lanes: lanes cooperating on one packet (0 = automatic, else
  * 1/2/4).  wg_per_cu: resident 256-thread workgroups per CU of the persistent

@@ -49,6 +49,12 @@ SIGNATURES = {
                                                 c_size, c_vp, c_vp, c_vp, c_vp]),
     "rg_handshake_finish_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_size,
                                               c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "rg_peer_ts_workspace_size": (c_size, [c_size, c_u32]),
+    "rg_peer_ts_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_size, c_vp]),
+    "rg_peer_cookie_consume_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp,
+                                                 c_size, c_vp, c_vp, c_vp, c_vp]),
+    "rg_peer_cookies_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_size, c_vp, c_vp, c_vp]),
+    "rg_peer_mac1_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_u32, c_u32, c_size, c_vp, c_vp]),
     "rg_rx_table_build": (c_int, [c_vp, c_vp, c_size, c_vp, ctypes.c_uint32]),
     "rg_rx_table_find": (ctypes.c_int64, [c_vp, ctypes.c_uint32, ctypes.c_uint32]),
     "rg_open_batch_dev_rx": (c_int, [c_vp, c_vp, ctypes.c_uint32, c_vp, ctypes.c_uint32, c_vp, c_size, c_vp, c_size,

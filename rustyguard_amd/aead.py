@@ -16,6 +16,10 @@ Reference interface -> this module
   encrypt_handshake_init (lib.rs:287-344), decrypt_handshake_resp + split(true)
     (lib.rs:435-465)                     -> Engine.handshake_initiate_dev,
                                             handshake_finish_dev, pending_table
+  Peer {latest_ts, cookie, last_sent_mac1} (rustyguard-core/src/lib.rs:170-180),
+    the timestamp check (handshake.rs:88-91), handle_cookie (handshake.rs:233-257)
+                                         -> Engine.peer_ts_dev, peer_cookie_consume_dev,
+                                            peer_cookies_dev, peer_mac1_dev
   batched hot path                        -> Engine.seal_dev/open_dev (device
                                              tensors), seal_host/open_host (numpy)
   Sessions send/recv of data frames       -> Sessions.send_batch / recv_batch
@@ -36,6 +40,7 @@ PKT_OK, PKT_DECRYPT_ERR, PKT_INVALID, PKT_REJECTED, PKT_UNALIGNED, PKT_NOT_DATA,
 PKT_COOKIE = 7  # rg_cookie_reply_batch_dev: a cookie reply was written for this message
 PKT_KEYEXCHANGE = 8  # Error::KeyExchangeError: an all-zero X25519 result (x25519_dev, the handshake calls)
 PEER_NONE = 0xFFFFFFFF
+PEER_STATE_BYTES = 64  # rg_hs_peer_state: latest_ts[12], has_cookie u32, cookie[16], last_sent_mac1[16], pad[16]
 RECV_AUTHENTICATED, RECV_KEEPALIVE = 1, 2
 KEY_SCAN = 0xFFFFFFFE  # rg_mac_verify_batch_dev: try every key
 KEY_SKIP = 0xFFFFFFFF
@@ -303,6 +308,70 @@ class Engine:
                                                           _vp(transport_keys), _vp(pend_idx_out), _vp(remote_out),
                                                           _vp(claim), _vp(status), _stream_handle(stream)),
                     "rg_handshake_finish_batch_dev")
+
+    def peer_ts_workspace(self, n: int, npeers: int, device=None):
+        """The scratch tensor (uint8, on this engine's device) peer_ts_dev needs for n rows over npeers peers
+        (rg_peer_ts_workspace_size)."""
+        import torch
+
+        size = int(self._L.rg_peer_ts_workspace_size(n, npeers))
+        if size == 0:
+            raise _lib.RgError(f"no workspace can hold a batch of {n} rows")
+        return torch.empty(size, dtype=torch.uint8, device=device if device is not None else f"cuda:{self.device}")
+
+    def peer_ts_dev(self, state, results, status, peers_out, workspace=None, stream=None):
+        """The timestamp-replay check of handle_handshake_init, in order per peer, behind handshake_init_dev
+        (rg_peer_ts_batch_dev): state = PEER_STATE_BYTES (64) bytes per peer, results / status = what
+        handshake_init_dev wrote (updated in place: an older timestamp becomes PKT_REJECTED and its row is
+        wiped), peers_out = uint32 per row (the peer of a row that is still PKT_OK, PEER_NONE otherwise).
+        Returns the workspace used."""
+        n = _nbytes(status)
+        npeers = _nbytes(state) // PEER_STATE_BYTES
+        assert _nbytes(state) % PEER_STATE_BYTES == 0 and _nbytes(results) >= 128 * n and _nbytes(peers_out) >= 4 * n
+        if workspace is None:
+            workspace = self.peer_ts_workspace(n, npeers)
+        self._check(self._L.rg_peer_ts_batch_dev(self._h, _vp(state), npeers, _vp(results), _vp(status),
+                                                 _vp(peers_out), n, _vp(workspace), _nbytes(workspace),
+                                                 _stream_handle(stream)), "rg_peer_ts_batch_dev")
+        return workspace
+
+    def peer_cookie_consume_dev(self, state, cookie_keys, sess_table, desc, gate, buf, cookies_out, claim, status,
+                                stream=None):
+        """handle_cookie for a batch of CookieMessages (rg_peer_cookie_consume_batch_dev): cookie_keys = 32 bytes
+        per peer (cookie_key of its public key), sess_table = rx_table(our session ids, their peer rows) on the
+        device, gate = one status byte per message or None, cookies_out = 16 bytes per message, claim = uint32
+        per peer (workspace).  The cookie of the highest valid message index per peer is stored in state."""
+        n = _ndesc(desc)
+        npeers = _nbytes(state) // PEER_STATE_BYTES
+        assert _nbytes(state) % PEER_STATE_BYTES == 0 and _nbytes(cookie_keys) >= 32 * npeers
+        assert _nbytes(cookies_out) >= 16 * n and _nbytes(claim) >= 4 * npeers and _nbytes(status) >= n
+        assert gate is None or _nbytes(gate) >= n
+        self._check(self._L.rg_peer_cookie_consume_batch_dev(self._h, _vp(state), npeers, _vp(cookie_keys),
+                                                             _vp(sess_table), _nbytes(sess_table) // 8, _vp(desc),
+                                                             _vp(gate), n, _vp(buf), _nbytes(buf), _vp(cookies_out),
+                                                             _vp(claim), _vp(status), _stream_handle(stream)),
+                    "rg_peer_cookie_consume_batch_dev")
+
+    def peer_cookies_dev(self, state, peer_idx, cookies_out, has_cookie_out, stream=None):
+        """The cookies / has_cookie arrays of handshake_initiate_dev and handshake_resp_dev out of the peer state
+        table (rg_peer_cookies_batch_dev): peer_idx = uint32 per row (PEER_NONE: no cookie)."""
+        n = _nbytes(has_cookie_out)
+        assert _nbytes(state) % PEER_STATE_BYTES == 0 and _nbytes(peer_idx) >= 4 * n and _nbytes(cookies_out) >= 16 * n
+        self._check(self._L.rg_peer_cookies_batch_dev(self._h, _vp(state), _nbytes(state) // PEER_STATE_BYTES,
+                                                      _vp(peer_idx), n, _vp(cookies_out), _vp(has_cookie_out),
+                                                      _stream_handle(stream)), "rg_peer_cookies_batch_dev")
+
+    def peer_mac1_dev(self, state, peer_idx, status, messages, stride: int, mac1_offset: int, claim, stream=None):
+        """peer.last_sent_mac1 after a send (rg_peer_mac1_batch_dev): the mac1 field of the highest PKT_OK row of
+        each peer.  (stride, mac1_offset) = (160, 116) for handshake_initiate_dev's messages, (96, 60) for
+        handshake_resp_dev's responses; claim = uint32 per peer (workspace)."""
+        n = _nbytes(status)
+        npeers = _nbytes(state) // PEER_STATE_BYTES
+        assert _nbytes(state) % PEER_STATE_BYTES == 0 and _nbytes(peer_idx) >= 4 * n and _nbytes(claim) >= 4 * npeers
+        assert _nbytes(messages) >= stride * n
+        self._check(self._L.rg_peer_mac1_batch_dev(self._h, _vp(state), npeers, _vp(peer_idx), _vp(status),
+                                                   _vp(messages), stride, mac1_offset, n, _vp(claim),
+                                                   _stream_handle(stream)), "rg_peer_mac1_batch_dev")
 
     def replay_workspace(self, n: int, nwin: int, device=None):
         """The scratch tensor (uint8, on this engine's device) that replay_batch_dev / recv_batch_dev_resident

@@ -38,6 +38,12 @@
          alone beside them.  Medians of seven with min-max, by stream events and by host wall clock.  Also
          written to profiles/route_bench.json
 
+  peerstate  the device-resident peer handshake state at 64 Ki and 1 Ki rows: the responder chain (init -> ts ->
+         cookies -> resp -> mac1) against init + resp alone, the initiator chain (cookies -> initiate -> mac1)
+         against initiate alone, and rg_peer_ts_batch_dev, rg_peer_cookies_batch_dev, rg_peer_mac1_batch_dev and
+         rg_peer_cookie_consume_batch_dev each alone, by stream events, medians of seven with min-max.  Also
+         written to profiles/peerstate_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -785,13 +791,144 @@ def initiator_leg(eng):
     return out
 
 
+def peerstate_leg(eng):
+    """The device-resident peer handshake state at 64 Ki and 1 Ki rows, by stream events, medians of seven with
+    min-max, all in one run: the responder chain (init -> ts -> cookies -> resp -> mac1) against init + resp alone
+    on the same messages, the initiator chain (cookies -> initiate -> mac1) against initiate alone, and each new
+    call alone (ts with all rows on one peer and with every row on a peer of its own).  Every row carries the same
+    timestamp, which passes (equal to latest), so every call does its whole work in every repetition.  Written to
+    profiles/peerstate_bench.json."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import handshake_cases as hc  # the Python model makes the valid messages
+    import peerstate_cases as pc
+
+    r = hc.Responder(53, npeers=8, neph=256)
+    rng = np.random.default_rng(59)
+    rb = lambda k: rng.integers(0, 256, k, dtype=np.uint8).tobytes()  # noqa: E731
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")  # noqa: E731
+    stamp = hc.tai64n(1_800_000_000, 7)
+    base = np.zeros((256, 160), np.uint8)
+    for i in range(256):
+        base[i, :148] = np.frombuffer(hc.make_initiation(r.sk_i[i % 8], r.pk_r, r.esk_i[i], stamp, i)[0], np.uint8)
+    peers = hc.peer_rows(r.peers)
+    d_own, d_peers, d_table = dev(r.own), dev(peers), dev(aead.peer_table(peers))
+    # the initiator of the second chain: 8 peer rows, dealt round robin
+    sk_a = rb(32)
+    a_own = dev(np.frombuffer(sk_a + hc.pubkey(sk_a), np.uint8))
+    # 256 valid cookie messages over the 8 peers, each under its peer's recorded mac1
+    ckeys = [pc.cookie_key(p[0]) for p in r.peers]
+    state8 = [pc.state_row(mac1=rb(16)) for _ in range(8)]
+    ids = np.arange(256, dtype=np.uint32) + 0x7000_0000
+    cmsg = np.frombuffer(b"".join(pc.cookie_message(int(ids[i]), rb(24), ckeys[i % 8], state8[i % 8][32:48], rb(16))
+                                  for i in range(256)), np.uint8).reshape(256, 64)
+    d_ckeys = dev(np.frombuffer(b"".join(ckeys), np.uint8))
+    d_sess = dev(aead.rx_table(ids, (np.arange(256) % 8).astype(np.uint32)))
+
+    def ev_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    def stats(ts, n):
+        ts = sorted(ts)
+        med = ts[len(ts) // 2]
+        return {"ms_median": round(med, 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4),
+                "per_s_median": round(n / med * 1e3)}
+
+    out = {}
+    for n in (1 << 16, 1 << 10):
+        buf = dev(np.tile(base, (n // 256, 1)).reshape(-1))
+        desc = np.zeros(n, DESC_DTYPE)
+        desc["offset"], desc["len"] = np.arange(n, dtype=np.uint64) * 160, 148
+        d_desc = dev(desc.view(np.uint8).reshape(-1, 16))
+        cdesc = np.zeros(n, DESC_DTYPE)
+        cdesc["offset"], cdesc["len"] = np.arange(n, dtype=np.uint64) * 64, 64
+        d_cdesc, d_cbuf = dev(cdesc.view(np.uint8).reshape(-1, 16)), dev(np.tile(cmsg, (n // 256, 1)).reshape(-1))
+        state, claim = dev(pc.rows_array(state8, 64)), z(8, dtype=torch.int32)
+        res, st, st2, po = z(n, 128), z(n), z(n), z(n, dtype=torch.int32)
+        esk, sids = dev(rng.integers(0, 256, (n, 32), dtype=np.uint8)), dev(np.arange(n, dtype=np.uint32))
+        resp, keys, cookies, has = z(n, 96), z(n, 64), z(n, 16), z(n)
+        ws = eng.peer_ts_workspace(n, 8)
+        ini = lambda: eng.handshake_init_dev(d_own, d_peers, d_table, d_desc, None, buf, res, st)  # noqa: E731
+        rsp0 = lambda: eng.handshake_resp_dev(d_peers, res, None, esk, sids, None, None, resp, keys, st2)  # noqa: E731
+        tsc = lambda: eng.peer_ts_dev(state, res, st, po, workspace=ws)  # noqa: E731
+        gat = lambda: eng.peer_cookies_dev(state, po, cookies, has)  # noqa: E731
+        rsp = lambda: eng.handshake_resp_dev(d_peers, res, st, esk, sids, cookies, has, resp, keys, st2)  # noqa: E731
+        rec = lambda: eng.peer_mac1_dev(state, po, st2, resp, 96, 60, claim)  # noqa: E731
+        chain = lambda: (ini(), tsc(), gat(), rsp(), rec())  # noqa: E731
+        # the initiator's side
+        pidx, tss = dev((np.arange(n) % 8).astype(np.uint32)), dev(np.tile(np.frombuffer(stamp, np.uint8), (n, 1)))
+        msgs, pending, st3 = z(n, 160), z(n, 128), z(n)
+        gat_i = lambda: eng.peer_cookies_dev(state, pidx, cookies, has)  # noqa: E731
+        init0 = lambda: eng.handshake_initiate_dev(a_own, d_peers, pidx, None, esk, tss, sids, None, None, msgs,  # noqa: E731
+                                                   pending, st3)
+        init = lambda: eng.handshake_initiate_dev(a_own, d_peers, pidx, None, esk, tss, sids, cookies, has, msgs,  # noqa: E731
+                                                  pending, st3)
+        rec_i = lambda: eng.peer_mac1_dev(state, pidx, st3, msgs, 160, 116, claim)  # noqa: E731
+        chain_i = lambda: (gat_i(), init(), rec_i())  # noqa: E731
+        # each call alone; ts on crafted rows: one peer, and a peer per row
+        one = dev(pc.rows_array([pc.result_row(stamp, 0)], 128)).repeat(n, 1)
+        many = one.clone()
+        many[:, 108:112] = dev(np.arange(n, dtype=np.uint32).view(np.uint8).reshape(n, 4))
+        st_ok, po2, state_n, ws_n = z(n), z(n, dtype=torch.int32), z(n, 64), eng.peer_ts_workspace(n, n)
+        ts_one = lambda: eng.peer_ts_dev(state, one, st_ok, po2, workspace=ws)  # noqa: E731
+        ts_many = lambda: eng.peer_ts_dev(state_n, many, st_ok, po2, workspace=ws_n)  # noqa: E731
+        got_ck, st4 = z(n, 16), z(n)
+        state_c = dev(pc.rows_array(state8, 64))  # a table of its own: the chains' mac1 calls rewrite the AAD
+        con = lambda: eng.peer_cookie_consume_dev(state_c, d_ckeys, d_sess, d_cdesc, None, d_cbuf, got_ck, claim, st4)  # noqa: E731
+        chain(), chain_i(), ts_one(), ts_many()
+        torch.cuda.synchronize()
+        assert (st == aead.PKT_OK).all().item() and (st2 == aead.PKT_OK).all().item() and (st3 == aead.PKT_OK).all().item()
+        assert (st_ok == aead.PKT_OK).all().item() and torch.equal(po2.cpu(), torch.arange(n, dtype=torch.int32))
+        con()
+        torch.cuda.synchronize()
+        assert (st4 == aead.PKT_OK).all().item()
+        t = {k: [] for k in ("init_resp", "responder_chain", "initiate", "initiator_chain", "ts_one_peer",
+                             "ts_peer_per_row", "ts_8_peers_in_chain", "cookies", "mac1_resp", "mac1_init", "consume")}
+        for _ in range(7):
+            t["init_resp"].append(ev_ms(lambda: (ini(), rsp0())))
+            t["responder_chain"].append(ev_ms(chain))
+            t["initiate"].append(ev_ms(init0))
+            t["initiator_chain"].append(ev_ms(chain_i))
+            ini()
+            torch.cuda.synchronize()
+            t["ts_8_peers_in_chain"].append(ev_ms(tsc))
+            t["ts_one_peer"].append(ev_ms(ts_one))
+            t["ts_peer_per_row"].append(ev_ms(ts_many))
+            t["cookies"].append(ev_ms(gat_i))
+            t["mac1_resp"].append(ev_ms(rec))
+            t["mac1_init"].append(ev_ms(rec_i))
+            t["consume"].append(ev_ms(con))
+        assert (st2 == aead.PKT_OK).all().item() and (st4 == aead.PKT_OK).all().item()
+        row = {k: stats(v, n) for k, v in t.items()}
+        row["responder_chain_extra_ms"] = round(row["responder_chain"]["ms_median"] - row["init_resp"]["ms_median"], 4)
+        row["initiator_chain_extra_ms"] = round(row["initiator_chain"]["ms_median"] - row["initiate"]["ms_median"], 4)
+        out[f"rows_{n}"] = row
+    out["note"] = ("stream events around each sequence of calls, medians of 7 repetitions after one warm-up round; rows "
+                   "are 256 distinct valid initiations over 8 peers, tiled, all with one timestamp (equal passes: no "
+                   "row is turned down); responder_chain = init + ts + cookies + resp + mac1, init_resp = init + resp; "
+                   "initiator_chain = cookies + initiate + mac1; ts = prep + the radix passes the peer count needs "
+                   "(none for one peer, 1 for 8, 2 for 1 Ki and for 64 Ki) + reduce + carry + verdict + advance; "
+                   "consume = memset + open + commit over 8 peers; mac1 = memset + claim + commit")
+    with open(os.path.join(root, "profiles", "peerstate_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
-    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator"]
+    legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
+                            "peerstate"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
-                      ("initiator", initiator_leg)):
+                      ("initiator", initiator_leg), ("peerstate", peerstate_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
