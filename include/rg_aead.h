@@ -95,6 +95,7 @@ enum rg_pkt_status {
                                the handshake calls) */
     RG_PKT_UNROUTABLE = 9,  /* cryptokey routing (rg_route_batch_dev, rg_route_check_batch_dev): the inner address
                                matches no allowed prefix, or on receive a prefix of another peer */
+    RG_PKT_FULL = 10,       /* rg_session_install_batch_dev: the session table has no free row left */
 };
 
 /* Statuses fail closed.  A packet reads RG_PKT_OK only after the kernel that processed it wrote that
@@ -349,8 +350,8 @@ int rg_handshake_resp_batch_dev(rg_ctx *ctx, const rg_hs_peer *peers, uint32_t n
  * and be captured into a graph); n == 0 returns RG_OK; RG_EINVAL with nothing enqueued for a null required
  * pointer, n > 2^32 - 1 or a misaligned array.  Struct rows, desc, messages and transport_keys must be 16-byte
  * aligned, word arrays (peer_idx, esk, timestamps, session_ids, cookies, pend_table, pend_idx_out, remote_out,
- * claim) 4-byte aligned.  Session allocation, timers, the peer's endpoint and current_handshake stay with the
- * caller.
+ * claim) 4-byte aligned.  Choosing session ids, timers, the peer's endpoint and current_handshake stay with the
+ * caller; installing the finished sessions is rg_session_install_finish_batch_dev's (further down).
  *
  * Randomness and time: the library has no RNG and no clock.  esk[i] must be 32 fresh bytes of the caller's
  * CSPRNG for every row of every call (EphemeralPrivateKey::generate, handshake.rs:275), never reused;
@@ -987,6 +988,110 @@ int rg_send_batch_dev_routed(rg_ctx *ctx, const uint8_t *keys, const uint32_t *r
                              const uint64_t *now_ns, uint8_t *buf, size_t buf_len, uint32_t *peers_out,
                              uint8_t *status, uint64_t *counters_out, uint8_t *rekey_out, void *workspace,
                              size_t workspace_len, void *stream);
+
+/* ------------------------------ device-resident session table (batch, async) */
+/* The step between the handshake calls and the resident transport calls: a batch of finished handshakes becomes
+ * live rows of the tables rg_send_batch_dev_resident, rg_recv_batch_dev_resident, rg_route_batch_dev and
+ * rg_route_check_batch_dev take, on the stream that produced them, and sessions past their lifetime leave the
+ * tables the same way -- the tails of handle_handshake_init (rustyguard-core/src/handshake.rs:110-133) and
+ * handle_handshake_resp (:201-227) and the ExpireTransport timer (rustyguard-core/src/time.rs:84-98).  No key
+ * leaves the device.
+ *
+ * The conventions are the handshake and peer-state calls': every array is device memory; the calls enqueue on
+ * `stream` and return without waiting, allocate nothing and keep nothing in the context (so they can be
+ * captured into a graph); n == 0 returns RG_OK; RG_EINVAL with nothing enqueued for a null required pointer
+ * (gate, now_ns, rows and expired_out are optional), n > 2^32 - 1, a misaligned array, rx_cap not a power of
+ * two or < 2 nkeys, or a workspace smaller than rg_session_workspace_size(n, nkeys, npeers) reports (0 when the
+ * sizes are too large for any workspace; non-decreasing in each argument; n = 0 for the expire call).  The
+ * workspace is 16-byte aligned and belongs to one call at a time.  A lane stores its status after everything
+ * else it writes.
+ *
+ * rg_session_tables is a host struct of device pointers, read at call time.  The arrays are the caller's, the
+ * ones the resident calls take plus local_ids.  An empty table: slot_peer, peer_slot and rx_table filled with
+ * 0xFF, everything else zero.  rx_table must be current when a call starts: every call below leaves it so, and
+ * a caller that seeded rows itself runs rg_session_index_dev first. */
+typedef struct rg_session_tables {
+    uint8_t       *send_keys;   /* [nkeys][32]  keys of rg_send_batch_dev_resident            16-B aligned */
+    uint8_t       *recv_keys;   /* [nkeys][32]  keys of rg_recv_batch_dev_resident            16-B aligned */
+    uint32_t      *receivers;   /* [nkeys]      the peer's id for outgoing headers                          */
+    uint32_t      *local_ids;   /* [nkeys]      our id, what incoming headers name                          */
+    uint32_t      *slot_peer;   /* [nkeys]      peer of the row; RG_PEER_NONE = the row is free             */
+    rg_antireplay *windows;     /* [nkeys] */
+    rg_send_state *send_state;  /* [nkeys] */
+    rg_rx_entry   *rx_table;    /* [rx_cap]     8-byte aligned; rx_cap a power of two >= 2 nkeys           */
+    uint32_t      *peer_slot;   /* [npeers]     the peer's current row; RG_KEY_SKIP = none                  */
+    uint32_t nkeys, rx_cap, npeers;
+} rg_session_tables;
+
+/* rg_session_install_batch_dev.  Its result equals this loop, bit for bit on status, rows_out, transport_keys and
+ * every array of the tables except the byte layout of rx_table:
+ *   free = the rows r with slot_peer[r] == RG_PEER_NONE before the call, ascending
+ *   seen = the local_ids of the rows that are live before the call
+ *   for i in 0..n, in array order:
+ *     rows_out[i] = RG_KEY_SKIP
+ *     if gate && gate[i] != RG_PKT_OK: status[i] = RG_PKT_REJECTED; nothing else of row i is read or written
+ *     zero transport_keys[i] once its 64 bytes are read     (a key row is consumed once, whatever follows)
+ *     if peers[i] >= npeers:           status[i] = RG_PKT_INVALID
+ *     elif local_ids[i] in seen:       status[i] = RG_PKT_REJECTED
+ *     else: seen += local_ids[i]                            (before the capacity check)
+ *       if free is exhausted:          status[i] = RG_PKT_FULL
+ *       else: r = next of free
+ *         send_keys[r], recv_keys[r] = transport_keys[i][0:32], [32:64]
+ *         receivers[r] = remote_ids[i]; local_ids[r] = local_ids[i]; slot_peer[r] = peers[i]
+ *         windows[r] = zero; send_state[r] = {0, now, now}  (now = *now_ns, 0 when now_ns is NULL)
+ *         peer_slot[peers[i]] = r                           (peer.current_transport: the last in array order)
+ *         rows_out[i] = r; status[i] = RG_PKT_OK
+ *   rx_table = the receiver table over { (local_ids[r], r) : slot_peer[r] != RG_PEER_NONE }
+ * The peer's previous row is left alone: the reference, too, keeps an old session receiving until it expires.
+ * Once free runs out every later eligible row is RG_PKT_FULL, so whether a row repeats an earlier eligible row
+ * does not depend on who got a row.  Computed in parallel, nothing decided by arrival order: the live ids by a
+ * read of rx_table as it stands, ids inside the batch by an atomicMin of the index in a table in the workspace,
+ * rows by an exclusive count of the eligible handshakes and a compaction of the free rows, peer_slot by
+ * atomicMax(claim[p], i + 1) and a commit over the peers.  All n statuses are RG_PKT_PENDING first.
+ *
+ * rx_table is rebuilt at the end of every call that changes rows: a memset to 0xFF, then one lane per live row
+ * claims the first empty entry from its home slot.  Which of two colliding rows gets the earlier entry depends
+ * on arrival; what rg_rx_table_find and the kernels' lookup answer does not.  Probing is bounded by rx_cap.
+ *
+ * The wrappers take the handshake calls' outputs as they are, through the same kernels:
+ *   rg_session_install_resp_batch_dev    local id session_ids[i], remote id results[i].sender, peer
+ *                                        results[i].peer, keys rg_handshake_resp_batch_dev's transport_keys
+ *   rg_session_install_finish_batch_dev  local id pend_session_ids[pend_idx_out[i]], peer
+ *                                        pend_peers[pend_idx_out[i]], remote id remote_out[i], keys
+ *                                        rg_handshake_finish_batch_dev's transport_keys; pend_session_ids and
+ *                                        pend_peers are the session_ids and peer_idx the initiate call was given;
+ *                                        pend_idx_out[i] >= npending on a row whose gate is OK: RG_PKT_INVALID
+ * gate is the status array of the call whose outputs they take.
+ *
+ * rg_session_expire_batch_dev: one lane per row.  A live row r leaves if now_ns and
+ * send_state[r].started_ns + 180e9 < *now_ns (u64 wrapping add, strict <: rg_send_reserve_batch_dev's rule,
+ * should_expire), or if rows[m] names it (rg_sessions_remove; entries >= nkeys are ignored).  Its two keys,
+ * window and send state are zeroed, receivers[r] = local_ids[r] = 0, peer_slot[p] = RG_KEY_SKIP only if it still
+ * names r (time.rs:93-95), slot_peer[r] = RG_PEER_NONE.  expired_out[nkeys] (may be NULL) gets 1 for a row that
+ * left and 0 for every other.  Then rx_table is rebuilt.
+ *
+ * rg_session_index_dev is that rebuild alone. */
+size_t rg_session_workspace_size(size_t n, uint32_t nkeys, uint32_t npeers);
+int rg_session_install_batch_dev(rg_ctx *ctx, const rg_session_tables *tables, const uint8_t *gate /* [n] or NULL */,
+                                 const uint32_t *local_ids /* [n] */, const uint32_t *remote_ids /* [n] */,
+                                 const uint32_t *peers /* [n] */, uint8_t *transport_keys /* [n][64], zeroed */,
+                                 size_t n, const uint64_t *now_ns, uint8_t *status /* [n] */,
+                                 uint32_t *rows_out /* [n] */, void *workspace, size_t workspace_len, void *stream);
+int rg_session_install_resp_batch_dev(rg_ctx *ctx, const rg_session_tables *tables, const uint8_t *gate,
+                                      const uint32_t *session_ids /* [n] */, const rg_hs_init_result *results,
+                                      uint8_t *transport_keys, size_t n, const uint64_t *now_ns, uint8_t *status,
+                                      uint32_t *rows_out, void *workspace, size_t workspace_len, void *stream);
+int rg_session_install_finish_batch_dev(rg_ctx *ctx, const rg_session_tables *tables, const uint8_t *gate,
+                                        const uint32_t *pend_idx_out /* [n] */, const uint32_t *remote_out /* [n] */,
+                                        const uint32_t *pend_session_ids /* [npending] */,
+                                        const uint32_t *pend_peers /* [npending] */, uint32_t npending,
+                                        uint8_t *transport_keys, size_t n, const uint64_t *now_ns, uint8_t *status,
+                                        uint32_t *rows_out, void *workspace, size_t workspace_len, void *stream);
+int rg_session_expire_batch_dev(rg_ctx *ctx, const rg_session_tables *tables, const uint64_t *now_ns /* or NULL */,
+                                const uint32_t *rows /* [m] or NULL */, size_t m,
+                                uint8_t *expired_out /* [nkeys] or NULL */, void *workspace, size_t workspace_len,
+                                void *stream);
+int rg_session_index_dev(rg_ctx *ctx, const rg_session_tables *tables, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

@@ -131,6 +131,15 @@ SIGNATURES = {
                                          c_vp]),
     "rg_send_batch_dev_routed": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_u32, c_vp, c_size, c_vp,
                                          c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_session_workspace_size": (c_size, [c_size, c_u32, c_u32]),
+    "rg_session_install_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_vp,
+                                             c_size, c_vp]),
+    "rg_session_install_resp_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_vp,
+                                                  c_size, c_vp]),
+    "rg_session_install_finish_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_size, c_vp,
+                                                    c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_session_expire_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_size, c_vp]),
+    "rg_session_index_dev": (c_int, [c_vp, c_vp, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

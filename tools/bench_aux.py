@@ -44,6 +44,13 @@
          rg_peer_cookie_consume_batch_dev each alone, by stream events, medians of seven with min-max.  Also
          written to profiles/peerstate_bench.json
 
+  session  the device-resident session table: rg_session_install_batch_dev of 1 Ki and 64 Ki finished handshakes
+         into tables of 64 Ki and 1 Mi rows, half full; rg_session_expire_batch_dev of 10 % of the rows;
+         rg_session_index_dev (the receiver-table rebuild every call pays) alone; and, for 1 Ki handshakes into
+         the 64 Ki table, what a caller does today on the same rows: keys and ids to pinned host memory,
+         rg_sessions_insert_peer per row, the mirror refresh of the next device call.  Medians of seven with
+         min-max, by stream events and by host wall clock.  Also written to profiles/session_install_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -921,14 +928,133 @@ def peerstate_leg(eng):
     return out
 
 
+def session_leg(eng):
+    """The device-resident session table, medians of seven with min-max by stream events and by host wall clock (a
+    device sync behind the call), all in one run.  Tables of 64 Ki and 1 Mi rows with every other row live; 1 Ki
+    and 64 Ki handshakes with fresh ids over 256 peers (into the 64 Ki table only 32 Ki rows are free: the rest
+    is RG_PKT_FULL, which is part of what is timed).  The table is put back from a saved copy between
+    repetitions, outside the timed region.  The host path is timed for 1 Ki handshakes into the 64 Ki table
+    alone: rg_sessions_insert_peer searches the table for a free row from the start, which takes minutes to fill
+    half of a 1 Mi table.  Written to profiles/session_install_bench.json."""
+    import ctypes
+    import time
+
+    from rustyguard_amd import session
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(61)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    words = lambda a: dev(np.asarray(a, np.uint32).view(np.int32))  # noqa: E731
+    npeers = 256
+
+    def measure(fn, reset):
+        ev, wall = [], []
+        for _ in range(8):  # the first is the warm-up
+            reset()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ev.append(a.elapsed_time(b))
+        st = lambda ts: {"ms_median": round(sorted(ts)[len(ts) // 2], 4), "ms_min": round(min(ts), 4),  # noqa: E731
+                         "ms_max": round(max(ts), 4)}
+        return {"gpu": st(ev[1:]), "wall": st(wall[1:])}
+
+    out = {}
+    for nkeys in (1 << 16, 1 << 20):
+        T = session.SessionTables(eng, nkeys, npeers)
+        live = np.arange(nkeys) % 2 == 0
+        T.slot_peer[:] = words(np.where(live, np.arange(nkeys) % npeers, 0xFFFFFFFF))
+        T.local_ids[:] = words(np.where(live, np.arange(nkeys) + 0x4000_0000, 0))
+        T.send_keys[:] = dev(rng.integers(0, 256, (nkeys, 32), dtype=np.uint8))
+        started = np.zeros((nkeys, 3), np.uint64)
+        started[:, 1] = np.where(np.arange(nkeys) % 10 == 0, 5, 10**12)  # every fifth live row is old: 10 % of the rows
+        T.send_state[:] = dev(started.view(np.uint8).reshape(nkeys, 24))
+        session.index_dev(eng, T)
+        saved = {name: getattr(T, name).clone() for name in session.ARRAYS}
+
+        def reset():
+            for name in session.ARRAYS:
+                getattr(T, name).copy_(saved[name])
+
+        d_now = dev(np.array([10**12], np.int64))
+        expired = torch.zeros(nkeys, dtype=torch.uint8, device="cuda")
+        row = {}
+        for n in (1 << 10, 1 << 16):
+            lids, rids = words(np.arange(n) + 0x7000_0000), words(np.arange(n) + 0x0100_0000)
+            peers, key_rows = words(np.arange(n) % npeers), dev(rng.integers(0, 256, (n, 64), dtype=np.uint8))
+            keys, st = key_rows.clone(), torch.zeros(n, dtype=torch.uint8, device="cuda")
+            rows_out = torch.zeros(n, dtype=torch.int32, device="cuda")
+            ws = session.session_workspace(eng, n, nkeys, npeers)
+
+            def reset_n():
+                reset()
+                keys.copy_(key_rows)
+
+            row[f"install_{n}"] = measure(lambda: session.install_batch_dev(eng, T, None, lids, rids, peers, keys, st,
+                                                                            rows_out, now_ns=d_now, workspace=ws), reset_n)
+            want_ok = min(n, nkeys // 2)
+            assert int((st == aead.PKT_OK).sum()) == want_ok and int((st == session.PKT_FULL).sum()) == n - want_ok
+        ws = session.session_workspace(eng, 0, nkeys, npeers)
+        row["expire_10_percent"] = measure(lambda: session.expire_batch_dev(eng, T, d_now, None, expired, workspace=ws), reset)
+        assert int(expired.sum()) == (nkeys + 9) // 10
+        row["rebuild"] = measure(lambda: session.index_dev(eng, T), reset)
+        out[f"table_{nkeys}"] = row
+
+    # what a caller does today: 1 Ki handshakes into a half-full host table of 64 Ki rows
+    n, nkeys = 1 << 10, 1 << 16
+    L = eng.library
+    S = aead.Sessions(eng, nkeys)
+    zero = (ctypes.c_uint8 * 32)()
+    for r in range(nkeys // 2):
+        L.rg_sessions_insert_peer(S._h, 0x4000_0000 + r, r, zero, zero, r % npeers)
+    d_keys, d_ids = dev(rng.integers(0, 256, (n, 64), dtype=np.uint8)), words(np.arange(3 * n))
+    h_keys = torch.zeros((n, 64), dtype=torch.uint8).pin_memory()
+    h_ids = torch.zeros(3 * n, dtype=torch.int32).pin_memory()
+    fdesc = dev(np.array([(0, 32, 0)], DESC_DTYPE).view(np.uint8).reshape(-1, 16))
+    fbuf, fst = torch.zeros(64, dtype=torch.uint8, device="cuda"), torch.zeros(1, dtype=torch.uint8, device="cuda")
+    slots = []
+
+    def host_path():
+        h_keys.copy_(d_keys, non_blocking=True)
+        h_ids.copy_(d_ids, non_blocking=True)
+        torch.cuda.synchronize()
+        base, ids = h_keys.data_ptr(), h_ids.numpy().view(np.uint32)
+        slots[:] = [L.rg_sessions_insert_peer(S._h, 0x7000_0000 + i, int(ids[n + i]), ctypes.c_void_p(base + 64 * i),
+                                              ctypes.c_void_p(base + 64 * i + 32), i % npeers) for i in range(n)]
+        S.send_batch_dev([slots[0]], fdesc, fbuf, fst)  # the next device call uploads the mirrors
+
+    def host_reset():
+        for r in slots:
+            L.rg_sessions_remove(S._h, r)
+        slots.clear()
+
+    out["host_path_1024_into_65536"] = measure(host_path, host_reset)
+    assert min(slots) >= 0
+    out["note"] = ("medians of 7 repetitions after one warm-up; gpu = stream events around the call, wall = host clock "
+                   "with a device sync behind it; tables half full (every other row live), handshakes with fresh ids "
+                   "over 256 peers; install = 4 memsets + prep + judge + carry + rank + free_count + carry + free_compact "
+                   "+ commit + peer_commit + the rebuild; expire = the expiry kernel + the rebuild; rebuild = memset + "
+                   "index kernel; host_path = keys and ids to pinned memory, rg_sessions_insert_peer per row from "
+                   "Python through ctypes, and a one-packet rg_send_batch_dev, whose mirror refresh uploads the table")
+    with open(os.path.join(root, "profiles", "session_install_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate"]
+                            "peerstate", "session"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
-                      ("initiator", initiator_leg), ("peerstate", peerstate_leg)):
+                      ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
