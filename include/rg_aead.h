@@ -677,6 +677,10 @@ typedef struct rg_sessions rg_sessions;
 /* REKEY_AFTER_MESSAGES / REJECT_AFTER_MESSAGES, rustyguard-core/src/lib.rs:63-65 */
 #define RG_REKEY_AFTER_MESSAGES (1ull << 60)
 #define RG_REJECT_AFTER_MESSAGES (0xFFFFFFFFFFFFFFFFull - (1ull << 13))
+/* KEEPALIVE_TIMEOUT / REKEY_AFTER_TIME / REJECT_AFTER_TIME, rustyguard-core/src/lib.rs:66-70, in nanoseconds */
+#define RG_KEEPALIVE_TIMEOUT_NS 10000000000ull
+#define RG_REKEY_AFTER_TIME_NS 120000000000ull
+#define RG_REJECT_AFTER_TIME_NS 180000000000ull
 
 int rg_sessions_create(rg_ctx *ctx, uint32_t capacity, rg_sessions **out);
 void rg_sessions_destroy(rg_sessions *s);
@@ -813,8 +817,8 @@ int rg_recv_batch_dev_finish(rg_sessions *s, const uint64_t *src, uint8_t *statu
  * with the other device calls: the one-stream rule above applies (a call on another stream while the
  * context's last batch is in flight fails with RG_EINVAL, nothing enqueued), and a buffer of the context
  * that has to grow does so outside a stream capture (run the shape once before capturing it).  The endpoint
- * and keepalive side effects of decrypt_packet (lib.rs:664-679) stay with the host session table: a caller
- * that wants them reads status and key_idx_out when it chooses to.
+ * side effect of decrypt_packet (lib.rs:670-679) stays with the caller, which reads status and key_idx_out
+ * when it chooses to; the keepalive side effect (:664-669) is rg_timer_note_recv_batch_dev behind this call.
  *
  * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer (undo, counters_out and
  * key_idx_out are optional), n > 2^32 - 1, windows not 8-byte or workspace not 16-byte aligned,
@@ -869,8 +873,8 @@ int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys,
  * the context's seal kernels and so shares its planner buffers with the other device calls: the one-stream
  * rule above applies (a call on another stream while the context's last batch is in flight fails with
  * RG_EINVAL, nothing enqueued), and a buffer of the context that has to grow does so outside a stream
- * capture (run the shape once before capturing it).  The keepalive timer stays with the caller, which reads
- * sent_ns when it chooses to.
+ * capture (run the shape once before capturing it).  The keepalive and rekey timers are the session-timer
+ * section's: rg_timer_note_send_batch_dev behind this call, rg_timer_turn_dev when the caller turns.
  *
  * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer (now_ns and rekey_out are
  * optional, for the resident call also counters_out), n > 2^32 - 1, state not 8-byte or workspace not 16-byte
@@ -1092,6 +1096,98 @@ int rg_session_expire_batch_dev(rg_ctx *ctx, const rg_session_tables *tables, co
                                 uint8_t *expired_out /* [nkeys] or NULL */, void *workspace, size_t workspace_len,
                                 void *stream);
 int rg_session_index_dev(rg_ctx *ctx, const rg_session_tables *tables, void *stream);
+
+/* ------------------------------ device-resident session timers (batch, async) */
+/* What Sessions::turn (rustyguard-core/src/time.rs:42-140, tick_timers) decides for transport sessions, on the
+ * stream that sends and receives: which sessions owe a keepalive and which peers owe a new handshake, as the
+ * arrays rg_send_batch_dev_resident and the initiator chain take.  Expiry stays rg_session_expire_batch_dev, run
+ * behind the turn.  The handshake-side timers (InitAttempt, ExpireHandshake, current_handshake) stay with the
+ * caller.
+ *
+ * The conventions are the session-table section's: every array is device memory; the calls enqueue on `stream`
+ * and return without waiting, allocate nothing and keep nothing in the context (so they can be captured into a
+ * graph); now_ns points at one uint64_t in device memory, read when the kernels run; n == 0 returns RG_OK;
+ * RG_EINVAL with nothing enqueued for a null required pointer (gate is optional, now_ns of the arm call when
+ * rekey_after_ns == 0, timers and send_state when nkeys == 0, the three lists when npeers == 0), n > 2^32 - 1, a
+ * misaligned array (timers, send_state, now_ns 8 bytes, word arrays 4, the workspace 16) or a workspace smaller
+ * than rg_timer_workspace_size(nkeys, npeers) reports (0 when either size is above 2^32 - 1; non-decreasing in
+ * each argument).  The workspace belongs to one call at a time.  A lane stores its output after everything else
+ * it writes.  All time arithmetic is the u64 wrapping add and strict < of rg_send_reserve_batch_dev.
+ *
+ * One rg_session_timer row runs parallel to every key-table row; the caller owns the array, and a zeroed row has
+ * nothing armed.  It holds what the reference's timer heap holds for a transport session. */
+#define RG_TIMER_KEEPALIVE_PENDING 1u /* Session.keepalive_pending */
+typedef struct rg_session_timer {    /* 16 bytes, 8-byte aligned */
+    uint64_t rekey_at_ns;            /* the RekeyAttempt heap entry: 0 = not armed, fires when rekey_at_ns < now */
+    uint32_t flags;                  /* RG_TIMER_KEEPALIVE_PENDING */
+    uint32_t pad;
+} rg_session_timer;
+
+/* rg_timer_arm_batch_dev runs behind an install, on its rows_out and status (as gate; NULL: every row passes): for
+ * every i with gate[i] == RG_PKT_OK and rows[i] < nkeys,
+ *   timers[rows[i]] = { rekey_after_ns ? *now_ns + rekey_after_ns : 0, 0, 0 }.
+ * rekey_after_ns is a host scalar: RG_REKEY_AFTER_TIME_NS for sessions we initiated (handshake.rs:218-222), 0 for
+ * sessions we responded to, where the reference arms no rekey.  Every install is followed by an arm: that is also
+ * what clears the stale row of a session that expired.
+ *
+ * rg_timer_note_send_batch_dev runs behind rg_send_batch_dev_resident or rg_send_batch_dev_routed, on their slots
+ * (for the routed send the slots at the head of its workspace's descriptors), status and rekey_out
+ * (lib.rs:564-570): for every i with status[i] == RG_PKT_OK, rekey_out[i] != 0 and slots[i] < nkeys, a
+ * rekey_at_ns that is 0 or greater than *now_ns becomes *now_ns.  Every lane that writes a row writes the same
+ * value.  A clock of 0 arms nothing (0 is "not armed").
+ *
+ * rg_timer_note_recv_batch_dev runs behind rg_recv_batch_dev_resident, on its key_idx_out and status, ahead of or
+ * beside rg_route_check_batch_dev (lib.rs:664-669; the reference, too, flags the keepalive before handle_extern):
+ * for every i with status[i] == RG_PKT_OK and k = key_idx[i] < nkeys, if
+ * send_state[k].sent_ns + RG_KEEPALIVE_TIMEOUT_NS < *now_ns the row's RG_TIMER_KEEPALIVE_PENDING is set (atomicOr).
+ *
+ * rg_timer_turn_dev is tick_timers for the whole table in one pass.  Of the tables it reads slot_peer, send_state,
+ * peer_slot, nkeys and npeers and writes none.  Its result equals this loop, bit for bit on every byte of timers,
+ * on ka_slots_out, rekey_peers_out and rekey_gate_out over their full npeers entries and on counts_out; every
+ * decision reads the state as it stands before the call:
+ *   now = *now_ns;  want_ka[p] = want_rk[p] = 0
+ *   for r in 0..nkeys with p = slot_peer[r] != RG_PEER_NONE and p < npeers:        (free rows are not touched)
+ *     if timers[r].flags & RG_TIMER_KEEPALIVE_PENDING:                              (time.rs:114-125)
+ *       clear it;  if send_state[r].sent_ns + 10e9 < now: want_ka[p] = 1
+ *     if timers[r].rekey_at_ns != 0 and timers[r].rekey_at_ns < now:                (time.rs:49-66; popped)
+ *       timers[r].rekey_at_ns = 0
+ *       if send_state[r].started_ns + 120e9 < now
+ *          or send_state[r].counter >= RG_REKEY_AFTER_MESSAGES: want_rk[p] = 1
+ *   nka = nrk = 0
+ *   for p ascending:
+ *     c = peer_slot[p]
+ *     if want_ka[p] and c < nkeys and slot_peer[c] == p                             (encrypt_message,
+ *        and not (send_state[c].started_ns + 180e9 < now                             lib.rs:249-265: the peer's
+ *                 or send_state[c].counter >= RG_REJECT_AFTER_MESSAGES):             CURRENT row, should_reject)
+ *       ka_slots_out[nka++] = c
+ *     if want_rk[p]: rekey_peers_out[nrk++] = p
+ *   ka_slots_out[nka..npeers) = RG_KEY_SKIP;  rekey_peers_out[nrk..npeers) = RG_PEER_NONE
+ *   rekey_gate_out[k] = RG_PKT_OK for k < nrk, RG_PKT_REJECTED above;  counts_out = {nka, nrk}
+ * computed with one lane per row, one lane per peer and an exclusive count over the peers; want_ka / want_rk get
+ * the same value from every row of a peer.  The padding lets the next calls run with the host-side n = npeers and
+ * no read-back: ka_slots_out is the slots of rg_send_batch_dev_resident over a fixed descriptor array of 32-byte
+ * frames with len = 0 (RG_KEY_SKIP rows are RG_PKT_REJECTED there, no counter taken, frame untouched; the send
+ * stores sent_ns = now); rekey_peers_out and rekey_gate_out are the peer_idx and gate of
+ * rg_handshake_initiate_batch_dev and rg_peer_mac1_batch_dev.
+ *
+ * Unlike the reference: a peer gets at most one keepalive a turn, decided on the state before the turn (the
+ * reference pops entries in time order, ties arbitrary, so two pending sessions of one peer yield one keepalive or
+ * two); a row holds one RekeyAttempt entry (the reference pushes one per send past REKEY_AFTER_MESSAGES);
+ * endpoints stay with the caller. */
+size_t rg_timer_workspace_size(size_t nkeys, size_t npeers);
+int rg_timer_arm_batch_dev(rg_ctx *ctx, rg_session_timer *timers, uint32_t nkeys, const uint32_t *rows /* [n] */,
+                           const uint8_t *gate /* [n] or NULL */, size_t n, const uint64_t *now_ns,
+                           uint64_t rekey_after_ns, void *stream);
+int rg_timer_note_send_batch_dev(rg_ctx *ctx, rg_session_timer *timers, uint32_t nkeys, const uint32_t *slots /* [n] */,
+                                 const uint8_t *status /* [n] */, const uint8_t *rekey_out /* [n] */, size_t n,
+                                 const uint64_t *now_ns, void *stream);
+int rg_timer_note_recv_batch_dev(rg_ctx *ctx, rg_session_timer *timers, const rg_send_state *send_state,
+                                 uint32_t nkeys, const uint32_t *key_idx /* [n] */, const uint8_t *status /* [n] */,
+                                 size_t n, const uint64_t *now_ns, void *stream);
+int rg_timer_turn_dev(rg_ctx *ctx, const rg_session_tables *tables, rg_session_timer *timers, const uint64_t *now_ns,
+                      uint32_t *ka_slots_out /* [npeers] */, uint32_t *rekey_peers_out /* [npeers] */,
+                      uint8_t *rekey_gate_out /* [npeers] */, uint32_t counts_out[2], void *workspace,
+                      size_t workspace_len, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

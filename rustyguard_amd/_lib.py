@@ -140,6 +140,11 @@ SIGNATURES = {
                                                     c_vp, c_vp, c_vp, c_size, c_vp]),
     "rg_session_expire_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_size, c_vp]),
     "rg_session_index_dev": (c_int, [c_vp, c_vp, c_vp]),
+    "rg_timer_workspace_size": (c_size, [c_size, c_size]),
+    "rg_timer_arm_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_u64, c_vp]),
+    "rg_timer_note_send_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
+    "rg_timer_note_recv_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_vp]),
+    "rg_timer_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

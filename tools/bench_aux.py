@@ -51,6 +51,12 @@
          rg_sessions_insert_peer per row, the mirror refresh of the next device call.  Medians of seven with
          min-max, by stream events and by host wall clock.  Also written to profiles/session_install_bench.json
 
+  timers  the device-resident session timers: rg_timer_turn_dev over tables of 64 Ki and 1 Mi rows (four rows per
+         peer) with about 1 % and about 50 % of the rows due, beside rg_session_expire_batch_dev on the same table;
+         the keepalive send over the turn's padded list (n = npeers) beside the same send over the due rows alone;
+         and rg_timer_arm_batch_dev, rg_timer_note_send_batch_dev and rg_timer_note_recv_batch_dev at 64 Ki
+         packets.  Medians of seven with min-max, by stream events.  Also written to profiles/timers_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -1047,14 +1053,117 @@ def session_leg(eng):
     return out
 
 
+def timers_leg(eng):
+    """The device-resident session timers by stream events, medians of seven with min-max, all in one run.  Every
+    row of the table is live, four rows per peer, the peer's current row its last; a due row is pending, silent
+    and carries a fired rekey entry on a session past REKEY_AFTER_TIME.  The timers and the send state are put back
+    from a saved copy between repetitions, outside the timed region.  Written to profiles/timers_bench.json."""
+    from rustyguard_amd import session, timers
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(71)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    words = lambda a: dev(np.asarray(a, np.uint32).view(np.int32))  # noqa: E731
+    now = 10**12
+    d_now = dev(np.array([now], np.int64))
+
+    def measure(fn, reset):
+        ev = []
+        for _ in range(8):  # the first is the warm-up
+            reset()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ev.append(a.elapsed_time(b))
+        ts = sorted(ev[1:])
+        return {"ms_median": round(ts[len(ts) // 2], 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4)}
+
+    out = {}
+    for nkeys in (1 << 16, 1 << 20):
+        npeers = nkeys // 4
+        T = session.SessionTables(eng, nkeys, npeers)
+        r = np.arange(nkeys)
+        T.slot_peer[:] = words(r % npeers)
+        T.peer_slot[:] = words(np.arange(npeers) + nkeys - npeers)
+        T.send_keys[:] = dev(rng.integers(0, 256, (nkeys, 32), dtype=np.uint8))
+        T.receivers[:] = words(r + 0x0100_0000)
+        T.local_ids[:] = words(r + 0x4000_0000)  # distinct ids: the rebuild behind the expiry probes a few entries
+        session.index_dev(eng, T)
+        tm = timers.timer_rows(eng, nkeys)
+        ka, rk = (torch.zeros(npeers, dtype=torch.int32, device="cuda") for _ in range(2))
+        gate, counts = torch.zeros(npeers, dtype=torch.uint8, device="cuda"), torch.zeros(2, dtype=torch.int32, device="cuda")
+        expired = torch.zeros(nkeys, dtype=torch.uint8, device="cuda")
+        ws_t, ws_x = timers.timer_workspace(eng, nkeys, npeers), session.session_workspace(eng, 0, nkeys, npeers)
+        desc = dev(np.array([(32 * k, 0, 0) for k in range(npeers)], DESC_DTYPE).view(np.uint8).reshape(-1, 16))
+        buf, st = torch.zeros(32 * npeers, dtype=torch.uint8, device="cuda"), torch.zeros(npeers, dtype=torch.uint8, device="cuda")
+        ws_s = eng.send_workspace(npeers, nkeys)
+        row = {"npeers": npeers}
+        for label, share in (("1_percent", 0.01), ("50_percent", 0.5)):
+            due = rng.random(nkeys) < share
+            state = np.zeros((nkeys, 3), np.uint64)
+            state[:, 0] = 3
+            state[:, 1] = np.where(due, now - 120 * 10**9 - 9, now - 9)
+            state[:, 2] = np.where(due, now - 10 * 10**9 - 9, now - 9)
+            rows_tm = np.zeros((nkeys, 2), np.uint64)
+            rows_tm[:, 0] = np.where(due, now - 1, now + 120 * 10**9)
+            rows_tm[:, 1] = due
+            saved_state, saved_tm = dev(state.view(np.uint8).reshape(nkeys, 24)), dev(rows_tm.view(np.uint8).reshape(nkeys, 16))
+
+            def reset():
+                T.send_state.copy_(saved_state)
+                tm.copy_(saved_tm)
+
+            turn = lambda: timers.turn_dev(eng, T, tm, d_now, ka, rk, gate, counts, workspace=ws_t)  # noqa: E731
+            res = {"turn": measure(turn, reset)}
+            nka, nrk = (int(x) for x in counts.cpu().numpy().view(np.uint32))
+            peers_due = int(np.bincount(r[due] % npeers, minlength=npeers).astype(bool).sum())
+            assert nka == nrk == peers_due, (nka, nrk, peers_due)
+            res["rows_due"], res["keepalives"], res["rekeys"] = int(due.sum()), nka, nrk
+            res["expire_none_due"] = measure(lambda: session.expire_batch_dev(eng, T, d_now, None, expired, workspace=ws_x),
+                                             reset)
+            assert int(expired.sum()) == 0
+            reset()
+            turn()
+            slots = ka.clone()  # the padded list: nka rows, then RG_KEY_SKIP
+            send = lambda m: eng.send_batch_dev_resident(T.send_keys, T.receivers, T.send_state, slots[:m], desc[:m],  # noqa: E731
+                                                         buf, st[:m], now_ns=d_now, workspace=ws_s)
+            res["keepalive_send_padded"] = measure(lambda: send(npeers), reset)
+            assert int((st == aead.PKT_OK).sum()) == nka
+            res["keepalive_send_due_only"] = measure(lambda: send(nka), reset)
+            assert int((st[:nka] == aead.PKT_OK).sum()) == nka
+            res["padded_send_over_turn"] = round(res["keepalive_send_padded"]["ms_median"] / res["turn"]["ms_median"], 2)
+            row[label] = res
+        if nkeys == 1 << 16:
+            n = 1 << 16
+            hit = words(rng.integers(0, nkeys, n))
+            ok, one = torch.zeros(n, dtype=torch.uint8, device="cuda"), torch.ones(n, dtype=torch.uint8, device="cuda")
+            row["arm_65536"] = measure(lambda: timers.arm_batch_dev(eng, tm, hit, ok, d_now, 120 * 10**9), reset)
+            row["note_send_65536"] = measure(lambda: timers.note_send_batch_dev(eng, tm, hit, ok, one, d_now), reset)
+            row["note_recv_65536"] = measure(lambda: timers.note_recv_batch_dev(eng, tm, T.send_state, hit, ok, d_now), reset)
+        out[f"table_{nkeys}"] = row
+    out["note"] = ("stream events around one call each, medians of 7 repetitions after one warm-up; every row live, four "
+                   "rows per peer; turn = clear + row + count + carry + compact kernels; expire = the expiry kernel + the "
+                   "receiver-table rebuild, no row leaving; keepalive sends of 32-byte frames, padded = n = npeers with "
+                   "RG_KEY_SKIP behind the due rows, due_only = n = the turn's count; the note and arm calls hit random "
+                   "rows of the 64 Ki table with every packet eligible")
+    with open(os.path.join(root, "profiles", "timers_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate", "session"]
+                            "peerstate", "session", "timers"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
-                      ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg)):
+                      ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg),
+                      ("timers", timers_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
