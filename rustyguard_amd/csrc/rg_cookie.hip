@@ -140,9 +140,9 @@ extern "C" int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys
     if (n == 0) return RG_OK;
     if (!keys || !desc || !addrs || !nonces || !buf || !replies || !status || n > 0xFFFFFFFFull)
         return set_err(RG_EINVAL, "cookie reply: bad args");
-    if (((uintptr_t)keys | (uintptr_t)replies) & 15u)
+    if (misaligned(keys, 16) || misaligned(replies, 16))
         return set_err(RG_EINVAL, "cookie reply: keys and replies must be 16-byte aligned");
-    if (((uintptr_t)addrs | (uintptr_t)nonces) & 7u)
+    if (misaligned(addrs, 8) || misaligned(nonces, 8))
         return set_err(RG_EINVAL, "cookie reply: addrs and nonces must be 8-byte aligned");
     rg::CookieArgs a{};
     a.keys = reinterpret_cast<const uint32_t *>(keys);
@@ -155,7 +155,7 @@ extern "C" int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys
     a.replies = replies;
     a.status = status;
     a.n = (uint32_t)n;
-    hipLaunchKernelGGL(rg::cookie_reply_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::cookie_reply_kernel, lanes(n), kWg, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "cookie reply launch");
     return RG_OK;
 }

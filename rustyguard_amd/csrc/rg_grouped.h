@@ -1,12 +1,18 @@
 // rg_grouped.h -- what a batch pass over packets grouped by a row shares: the device anti-replay commit
-// (rg_replay.hip: row = window, a segmented prefix maximum) and the device send-counter reservation
-// (rg_send.hip: row = session, a segmented count).  Device code and its launchers only.
+// (rg_replay.hip: row = window, a segmented prefix maximum), the device send-counter reservation
+// (rg_send.hip: row = session, a segmented count) and the peers' timestamp check (rg_peerstate.hip: row =
+// peer, a segmented prefix maximum).  Device code and its launchers only.
 //   Grouped          the device view of a batch and its grouped order; also the key of the radix passes
-//   SegPair          the segmented-scan monoid over a value type and an operation
+//   SegPair          the segmented-scan monoid over a value type and an operation; Tally the plain sum
 //   block_prefix     exclusive scan of one SegPair per lane over a workgroup, carry_kernel over the tiles'
 //                    aggregates
-//   GroupLayout      the workspace arrays every such pass has, group_rows their typed pointers and the order
-// How a tile of kGroupTile grouped packets is walked is each file's own: the walk follows the monoid.
+//   AggLayout        the tiles' aggregates in a workspace, Agg their typed pointers
+//   compact          the ordered compaction of an array: count, carry, rank.  Its users say what an item
+//                    contributes and what a ranked item does: the eligible handshakes and the free rows of
+//                    the session install (rg_session.hip), the two lists of the timer turn (rg_timers.hip)
+//   GroupLayout      the workspace arrays every grouped pass has, group_rows their typed pointers and the order
+// How a tile of kGroupTile grouped packets is walked is each segmented file's own: the walk follows the
+// monoid.  The plain sum has one walk, compact's.
 //
 // The grouping is stable, by the passes of an LSD radix sort over the 32-bit key, 8 bits per pass.  KeyOf is
 // a small struct passed by value with `__device__ uint32_t operator()(uint32_t i) const`: the grouping key
@@ -110,6 +116,84 @@ __global__ __launch_bounds__(256) void carry_kernel(uint32_t *agg_flag, typename
         agg_val[j] = ex.v;
         ex = join(ex, cur);
     }
+}
+
+// ------------------------------------------------------ ordered compaction
+// the plain sum: a SegPair whose f stays 0
+template <class V>
+struct Plus {
+    __device__ __forceinline__ V operator()(V a, V b) const { return a + b; }
+};
+template <class V>
+using Tally = SegPair<V, Plus<V>>;
+
+constexpr uint32_t kTileItems = kGroupTile / 256; // positions per lane of a tile, consecutive
+
+// The per-tile aggregates of a scan over n items, in this order in the caller's workspace.
+struct AggLayout {
+    uint64_t agg_val;  // [nblk] V and
+    uint64_t agg_flag; // [nblk] u32
+    uint32_t nblk;     // tiles of kGroupTile items
+    void take_agg(WorkspaceCursor &ws, uint64_t n, uint64_t value_size) {
+        nblk = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
+        agg_val = ws.take((uint64_t)nblk * value_size);
+        agg_flag = ws.take((uint64_t)nblk * 4);
+    }
+};
+template <class V>
+struct Agg {
+    V *val;
+    uint32_t *flag;
+    uint32_t nblk;
+    Agg(uint8_t *ws, const AggLayout &L)
+        : val(reinterpret_cast<V *>(ws + L.agg_val)), flag(reinterpret_cast<uint32_t *>(ws + L.agg_flag)),
+          nblk(L.nblk) {}
+};
+
+// A pass is a small struct passed by value.  Both walks call `V item(uint64_t pos) const` for every pos < n:
+// what the position contributes to the sum (several counts may share a V, each in bits of its own).  The
+// rank walk then calls `void emit(uint64_t pos, V v, V ex) const` with the contribution and the sum over
+// all positions below pos, and `void total(V all) const` once, with the sum over [0, n).  The passes of the
+// two walks may differ where the first has something to do once (the install's judging).
+template <class V, class Pass>
+__global__ __launch_bounds__(256) void compact_count_kernel(Pass p, uint32_t n, Agg<V> agg) {
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kTileItems;
+    V cnt = 0;
+    for (uint32_t k = 0; k < kTileItems; ++k)
+        if (base + k < n) cnt += p.item(base + k);
+    Tally<V> total;
+    (void)block_prefix(Tally<V>{0u, cnt}, total);
+    if (threadIdx.x == 0) {
+        agg.flag[blockIdx.x] = 0;
+        agg.val[blockIdx.x] = total.v;
+    }
+}
+template <class V, class Pass>
+__global__ __launch_bounds__(256) void compact_rank_kernel(Pass p, uint32_t n, Agg<V> agg) {
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kTileItems;
+    V v[kTileItems], cnt = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kTileItems; ++k) {
+        v[k] = base + k < n ? p.item(base + k) : V(0);
+        cnt += v[k];
+    }
+    Tally<V> total;
+    V ex = agg.val[blockIdx.x] + block_prefix(Tally<V>{0u, cnt}, total).v;
+    const V all = agg.val[blockIdx.x] + total.v; // everything up to this tile's end
+#pragma unroll
+    for (uint32_t k = 0; k < kTileItems; ++k) {
+        if (base + k < n) p.emit(base + k, v[k], ex);
+        ex += v[k];
+    }
+    if (blockIdx.x == agg.nblk - 1 && threadIdx.x == 0) p.total(all);
+}
+// count -> carry -> rank over [0, n) on st
+template <class V, class CountPass, class RankPass>
+inline void compact(CountPass count, RankPass rank, uint32_t n, const Agg<V> &agg, hipStream_t st) {
+    const dim3 tiles(agg.nblk), wg(256);
+    hipLaunchKernelGGL((compact_count_kernel<V, CountPass>), tiles, wg, 0, st, count, n, agg);
+    hipLaunchKernelGGL(carry_kernel<Tally<V>>, dim3(1), wg, 0, st, agg.flag, agg.val, agg.nblk);
+    hipLaunchKernelGGL((compact_rank_kernel<V, RankPass>), tiles, wg, 0, st, rank, n, agg);
 }
 
 // 8-bit passes that order keys below nkeys (0: one key, no grouping)
@@ -232,22 +316,19 @@ inline const uint32_t *group_by_key(KeyOf key, uint32_t n, uint32_t nblk, uint32
     return src;
 }
 
-// The workspace arrays of a grouped scan, contiguous and in this order in the caller's workspace.
-struct GroupLayout {
+// The workspace arrays of a grouped scan, contiguous and in this order in the caller's workspace: the two
+// orders, the histogram, then the per-tile aggregates of the segmented scan.
+struct GroupLayout : AggLayout {
     uint64_t order[2]; // [n] u32 each: packet indices grouped by row (ping-pong of the radix passes)
     uint64_t hist;     // [256][nblk] u32: digit counts per workgroup
-    uint64_t agg_val;  // [nblk] V and
-    uint64_t agg_flag; // [nblk] u32: per-tile aggregates of the segmented scan
-    uint32_t nblk;     // tiles of kGroupTile packets
     uint32_t passes;   // 8-bit radix passes over the row index (0: one row, no grouping)
     void take(WorkspaceCursor &ws, uint64_t n, uint32_t nrows, uint64_t value_size) {
-        nblk = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
+        const uint64_t tiles = (n + kGroupTile - 1) / kGroupTile;
         passes = radix_passes(nrows);
         order[0] = ws.take(passes > 0 ? n * 4 : 0);
         order[1] = ws.take(passes > 1 ? n * 4 : 0);
-        hist = ws.take(passes > 0 ? 256ull * nblk * 4 : 0);
-        agg_val = ws.take((uint64_t)nblk * value_size);
-        agg_flag = ws.take((uint64_t)nblk * 4);
+        hist = ws.take(passes > 0 ? 256ull * tiles * 4 : 0);
+        take_agg(ws, n, value_size);
     }
 };
 

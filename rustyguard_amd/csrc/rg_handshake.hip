@@ -630,7 +630,6 @@ __global__ __launch_bounds__(kHsWG) void handshake_commit_kernel(HsFinishArgs a)
 using namespace rg::host;
 
 namespace {
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 uint32_t grid(size_t n) { return (uint32_t)((n + rg::kHsWG - 1) / rg::kHsWG); }
 } // namespace
 

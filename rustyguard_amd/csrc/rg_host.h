@@ -1,15 +1,15 @@
 // rg_host.h -- private to the library's host side (never installed): the error and wait plumbing, the
 // buffer and event owners, the context and the group, shared by the host units (rg_ctx.cpp, rg_batch.cpp,
 // rg_hostpipe.cpp, rg_message.cpp, rg_sessions.cpp, rg_debug.cpp) and by the entry points that live beside
-// their kernels (rg_cookie.hip, rg_replay.hip, rg_send.hip, rg_peerstate.hip, rg_session.hip, rg_timers.hip).  Nothing here depends on
-// RG_TEST_HOOKS: the
-// test library's hooks are read through the four functions under "test hooks" below, defined in
-// rg_debug.cpp, and change no type's layout.
+// their kernels (rg_cookie.hip, rg_replay.hip, rg_send.hip, rg_handshake.hip, rg_route.hip, rg_peerstate.hip,
+// rg_session.hip, rg_timers.hip).  Nothing here depends on RG_TEST_HOOKS: the test library's hooks are read
+// through the four functions under "test hooks" below, defined in rg_debug.cpp, and change no type's layout.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -359,6 +359,18 @@ int fail_closed(int rc, uint8_t *status, size_t n);
 // send state) 8-byte aligned, the workspace 16-byte aligned and at least `total` bytes (0: the batch is
 // too large for any workspace).  RG_OK, or RG_EINVAL recorded under the call's name.
 int check_workspace(const char *what, const void *table, const void *workspace, size_t workspace_len, uint64_t total);
+
+// What the entry points beside their kernels share.  p is not a multiple of a, a power of two (null is aligned):
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+// one lane per item: the workgroup, and the grid of n items, computed in 64 bits
+inline const dim3 kWg(256);
+inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
+// RG_EINVAL, recorded as "what: why"
+inline int bad(const char *what, const char *why) {
+    char buf[200];
+    snprintf(buf, sizeof buf, "%s: %s", what, why);
+    return set_err(RG_EINVAL, buf);
+}
 
 } // namespace host
 } // namespace rg

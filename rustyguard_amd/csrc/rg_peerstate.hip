@@ -342,12 +342,6 @@ __global__ __launch_bounds__(256) void mac1_commit_kernel(Mac1Args a) {
 
 using namespace rg::host;
 
-namespace {
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-const dim3 kWg(256);
-} // namespace
-
 extern "C" size_t rg_peer_ts_workspace_size(size_t n, uint32_t npeers) { return (size_t)rg::ts_layout(n, npeers).total; }
 
 extern "C" int rg_peer_ts_batch_dev(rg_ctx *ctx, rg_hs_peer_state *state, uint32_t npeers, rg_hs_init_result *results,

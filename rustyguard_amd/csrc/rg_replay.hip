@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void replay_none_kernel(uint8_t *undo, uint32_
 hipError_t launch_commit(rg_antireplay *windows, uint32_t nwin, const uint32_t *win_idx, const uint64_t *counters,
                          uint32_t n, uint8_t *status, uint8_t *undo, uint8_t *ws, const ReplayLayout &L,
                          hipStream_t st) {
-    const dim3 per_packet((n + 255) / 256), wg(256);
+    const dim3 per_packet = host::lanes(n), wg = host::kWg;
     if (nwin == 0) {
         if (undo) hipLaunchKernelGGL(replay_none_kernel, per_packet, wg, 0, st, undo, n);
         return hipGetLastError();
@@ -419,7 +419,7 @@ extern "C" int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint
     a.undo = undo;
     a.udesc = reinterpret_cast<rg_pkt_desc *>(ws + L.udesc);
     a.counters_out = counters_out;
-    const dim3 grid((uint32_t)((n + 255) / 256)), wg(256);
+    const dim3 grid = lanes(n), wg = kWg;
     hipLaunchKernelGGL(rg::resident_gate_kernel, grid, wg, 0, st, a);
     RG_HIP(hipGetLastError(), "recv resident: gate launch");
     rc = rg_open_batch_dev(ctx, keys, nkeys, a.rdesc, n, buf, buf_len, status, counters_out, stream);

@@ -176,8 +176,6 @@ RoutedLayout routed_layout(uint64_t n, uint32_t nkeys) {
     return L;
 }
 
-dim3 per_packet(size_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-
 } // namespace
 } // namespace rg
 
@@ -209,11 +207,11 @@ extern "C" int rg_route_batch_dev(rg_ctx *ctx, const uint32_t *table, size_t tab
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!table || !peer_slot || !desc || !buf || !slots_out || !desc_out || !status || n > 0xFFFFFFFFull ||
-        table_words < rg::route::kRootWords || ((uintptr_t)buf & 15u))
+        table_words < rg::route::kRootWords || misaligned(buf, 16))
         return set_err(RG_EINVAL, "route: bad args");
     const rg::RouteArgs a{table, table_words, peer_slot, npeers, desc, (uint32_t)n, buf, buf_len,
                           peers_out, slots_out, desc_out, status};
-    hipLaunchKernelGGL(rg::route_kernel, rg::per_packet(n), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::route_kernel, lanes(n), kWg, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "route launch");
     return RG_OK;
 }
@@ -228,11 +226,11 @@ extern "C" int rg_route_check_batch_dev(rg_ctx *ctx, const uint32_t *table, size
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!table || !slot_peer || !desc || !key_idx || !buf || !status || n > 0xFFFFFFFFull ||
-        table_words < rg::route::kRootWords || ((uintptr_t)buf & 15u))
+        table_words < rg::route::kRootWords || misaligned(buf, 16))
         return set_err(RG_EINVAL, "route check: bad args");
     const rg::CheckArgs a{table, table_words, slot_peer, nkeys, desc, key_idx, (uint32_t)n, buf, buf_len,
                           status, inner_len_out};
-    hipLaunchKernelGGL(rg::check_kernel, rg::per_packet(n), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::check_kernel, lanes(n), kWg, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "route check launch");
     return RG_OK;
 }
@@ -250,7 +248,7 @@ extern "C" int rg_send_batch_dev_routed(rg_ctx *ctx, const uint8_t *keys, const 
     if (n == 0) return RG_OK;
     // everything the resident send would refuse is refused here, before the route kernel is enqueued
     if (!keys || !receivers || nkeys == 0 || !state || !table || !peer_slot || !desc || !buf || !status || !workspace ||
-        n > 0xFFFFFFFFull || table_words < rg::route::kRootWords || ((uintptr_t)buf & 15u))
+        n > 0xFFFFFFFFull || table_words < rg::route::kRootWords || misaligned(buf, 16))
         return set_err(RG_EINVAL, "send routed: bad args");
     const rg::RoutedLayout L = rg::routed_layout(n, nkeys);
     rc = check_workspace("send routed", state, workspace, workspace_len, L.total);
@@ -264,12 +262,12 @@ extern "C" int rg_send_batch_dev_routed(rg_ctx *ctx, const uint8_t *keys, const 
     uint8_t *verdict = ws + L.verdict;
     const rg::RouteArgs a{table, table_words, peer_slot, npeers, desc, (uint32_t)n, buf, buf_len,
                           peers_out, slots, wdesc, verdict};
-    hipLaunchKernelGGL(rg::route_kernel, rg::per_packet(n), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(rg::route_kernel, lanes(n), kWg, 0, st, a);
     RG_HIP(hipGetLastError(), "send routed: route launch");
     rc = rg_send_batch_dev_resident(ctx, keys, receivers, nkeys, state, slots, wdesc, n, now_ns, buf, buf_len, status,
                                     counters_out, rekey_out, ws + L.send, (size_t)L.send_len, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(rg::routed_overlay_kernel, rg::per_packet(n), dim3(256), 0, st, (const uint8_t *)verdict, status,
+    hipLaunchKernelGGL(rg::routed_overlay_kernel, lanes(n), kWg, 0, st, (const uint8_t *)verdict, status,
                        (uint32_t)n);
     RG_HIP(hipGetLastError(), "send routed: overlay launch");
     return RG_OK;

@@ -38,8 +38,8 @@
 namespace rg {
 namespace {
 
-constexpr uint64_t kRejectAfterTimeNs = 180ull * 1000000000ull; // REJECT_AFTER_TIME, lib.rs:204-209
-constexpr uint32_t kRounds = kGroupTile / 256;                  // rounds of 64 packets per wave
+constexpr uint64_t kRejectAfterTimeNs = RG_REJECT_AFTER_TIME_NS; // lib.rs:204-209
+constexpr uint32_t kRounds = kGroupTile / 256;                   // rounds of 64 packets per wave
 
 // Workspace of the device send calls (WorkspaceCursor, rg_internal.h).  total == 0: the batch is too large.
 // Every term is non-decreasing in n and in nkeys.
@@ -252,7 +252,7 @@ hipError_t launch_reserve(rg_send_state *state, uint32_t nkeys, const uint32_t *
     a.rekey_out = rekey_out;
     a.wdesc = reinterpret_cast<rg_pkt_desc *>(ws + L.wdesc);
     a.tot = reinterpret_cast<uint32_t *>(ws + L.tot);
-    const dim3 per_packet((n + 255) / 256), tiles(L.g.nblk), wg(256);
+    const dim3 per_packet = host::lanes(n), tiles(L.g.nblk), wg = host::kWg;
     if (nkeys == 0) {
         a.g.n = n;
         hipLaunchKernelGGL(send_none_kernel, per_packet, wg, 0, st, a);
@@ -319,8 +319,7 @@ extern "C" int rg_send_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, cons
     rc = rg_seal_batch_dev(ctx, keys, receivers, nkeys, reinterpret_cast<const rg_pkt_desc *>(ws + L.wdesc), ctr, n, buf,
                            buf_len, status, stream);
     if (rc) return rc;
-    hipLaunchKernelGGL(rg::send_overlay_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
-                       (const uint8_t *)verdict, status, (uint32_t)n);
+    hipLaunchKernelGGL(rg::send_overlay_kernel, lanes(n), kWg, 0, st, (const uint8_t *)verdict, status, (uint32_t)n);
     RG_HIP(hipGetLastError(), "send resident: overlay launch");
     return RG_OK;
 }

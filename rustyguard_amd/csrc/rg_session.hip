@@ -15,10 +15,10 @@
 //   prep      one lane per handshake: the gather of the wrapper, the gate, the peer bound, the duplicate check
 //             against the live rows (a read of the receiver table as it stands); every row that passes enters
 //             the batch's (id -> lowest index) table, an atomicMin of (id << 32 | index) per slot
-//   judge     the lowest index of an id is eligible, the others are duplicates; eligible rows counted per tile
-//   carry     rg_grouped.h: the tiles' counts -> what each tile starts from
-//   rank      every eligible row's rank among the eligible rows
-//   free_count / carry / free_compact   the same over the table: free_list[k] = the k-th free row, ascending
+//   compact   rg_grouped.h's count / carry / rank over the batch.  InstallJudge (the count walk): the lowest index
+//             of an id is eligible, the others are duplicates.  InstallRank (the rank walk): every eligible row's
+//             rank among the eligible rows
+//   compact   the same over the table, FreeRows in both walks: free_list[k] = the k-th free row, ascending
 //   commit    one lane per handshake: row = free_list[rank] or RG_PKT_FULL; the row's nine fields; the key row
 //             zeroed; atomicMax(claim[peer], i + 1)
 //   peer_commit  one lane per peer: peer_slot = the row of its highest installed index
@@ -31,23 +31,15 @@
 // The entry points' host side is here too (rg_peerstate.hip's precedent), on rg_host.h like the host units, none
 // of which names a launcher of this file.  All scratch is the caller's; nothing is allocated, waited for or kept
 // in the context.
-#include <cstdio>
-
 #include "rg_host.h"
 #include "rg_grouped.h"
 
 namespace rg {
 namespace {
 
-constexpr uint32_t kItems = kGroupTile / 256; // rows per lane in the scans, consecutive
-constexpr uint64_t kEmpty64 = ~0ull;          // a free entry of the id table and of the receiver table
+constexpr uint64_t kEmpty64 = ~0ull; // a free entry of the id table and of the receiver table
 constexpr uint32_t kWindowWords = sizeof(rg_antireplay) / 8;
-constexpr uint64_t kRejectAfterNs = 180000000000ull; // REJECT_AFTER_TIME
-
-struct Sum {
-    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
-};
-using Count = SegPair<uint32_t, Sum>; // f stays 0: a plain sum
+constexpr uint64_t kRejectAfterNs = RG_REJECT_AFTER_TIME_NS;
 
 // rg_session_tables as the kernels take it
 struct Tables {
@@ -64,14 +56,13 @@ struct SessionLayout {
     uint64_t lid, rid, peer; // [n] u32 each: the gathered ids and peer of a row that entered the id table
     uint64_t rank;           // [n] u32: prep's mark, judge's 0 / 1, then the rank among the eligible rows
     uint64_t ids;            // [ids_cap] u64: id << 32 | lowest index
-    uint64_t agg_n[2];       // [nblk_n] u32 each: counts and flags of the batch's tiles
-    uint64_t agg_k[2];       // [nblk_k] u32 each: of the table's tiles
+    AggLayout agg_n;         // u32 counts of the batch's tiles
+    AggLayout agg_k;         // of the table's tiles
     uint64_t free_list;      // [nkeys] u32
     uint64_t claim;          // [npeers] u32
     uint64_t mark;           // [nkeys] u8: rows an expire call names
     uint64_t total;
     uint64_t ids_cap; // a power of two >= 2 n, at most 2^32
-    uint32_t nblk_n, nblk_k;
 };
 SessionLayout session_layout(uint64_t n, uint32_t nkeys, uint32_t npeers) {
     SessionLayout L{};
@@ -79,15 +70,13 @@ SessionLayout session_layout(uint64_t n, uint32_t nkeys, uint32_t npeers) {
     WorkspaceCursor ws;
     L.ids_cap = 64;
     while (L.ids_cap < 2 * n && L.ids_cap < (1ull << 32)) L.ids_cap <<= 1;
-    L.nblk_n = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
-    L.nblk_k = (uint32_t)(((uint64_t)nkeys + kGroupTile - 1) / kGroupTile);
     L.lid = ws.take(n * 4);
     L.rid = ws.take(n * 4);
     L.peer = ws.take(n * 4);
     L.rank = ws.take(n * 4);
     L.ids = ws.take(L.ids_cap * 8);
-    for (int q = 0; q < 2; ++q) L.agg_n[q] = ws.take((uint64_t)L.nblk_n * 4);
-    for (int q = 0; q < 2; ++q) L.agg_k[q] = ws.take((uint64_t)L.nblk_k * 4);
+    L.agg_n.take_agg(ws, n, 4);
+    L.agg_k.take_agg(ws, nkeys, 4);
     L.free_list = ws.take((uint64_t)nkeys * 4);
     L.claim = ws.take((uint64_t)npeers * 4);
     L.mark = ws.take(nkeys);
@@ -115,8 +104,6 @@ struct InstallArgs {
     unsigned long long *ids;
     uint64_t ids_mask;
     uint32_t ids_shift;
-    uint32_t *agg_val, *agg_flag;   // the batch's tiles
-    uint32_t *kagg_val, *kagg_flag; // the table's tiles
     uint32_t *free_list, *claim;
     uint32_t n;
 };
@@ -199,13 +186,11 @@ __global__ __launch_bounds__(256) void install_prep_kernel(InstallArgs a) {
     ids_insert(a, lid, i);
 }
 
-// the first holder of an id is eligible; eligible rows per tile
-__global__ __launch_bounds__(256) void install_judge_kernel(InstallArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t cnt = 0;
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.n) break;
+// The two passes of rg_grouped.h's compact over the batch.  The count walk judges: the first holder of an id is
+// eligible (1), a later one a duplicate, answered here (0); rank[i] keeps the verdict.
+struct InstallJudge {
+    InstallArgs a;
+    __device__ __forceinline__ uint32_t item(uint64_t pos) const {
         const uint32_t i = (uint32_t)pos;
         uint32_t e = 0;
         if (a.rank[i] == kCandidate) {
@@ -216,63 +201,44 @@ __global__ __launch_bounds__(256) void install_judge_kernel(InstallArgs a) {
             }
         }
         a.rank[i] = e;
-        cnt += e;
+        return e;
     }
-    Count total;
-    (void)block_prefix(Count{0u, cnt}, total);
-    if (threadIdx.x == 0) {
-        a.agg_flag[blockIdx.x] = 0;
-        a.agg_val[blockIdx.x] = total.v;
+};
+// The rank walk reads that verdict: rank[i] = the row's rank among the eligible rows, or RG_KEY_SKIP.
+struct InstallRank {
+    uint32_t *rank;
+    __device__ __forceinline__ uint32_t item(uint64_t pos) const { return rank[pos]; }
+    __device__ __forceinline__ void emit(uint64_t pos, uint32_t e, uint32_t ex) const {
+        rank[pos] = e ? ex : RG_KEY_SKIP;
     }
-}
+    __device__ __forceinline__ void total(uint32_t) const {}
+};
+// The pass over the table: free_list[k] = the k-th free row, ascending (the entries behind the last stay
+// RG_KEY_SKIP).
+struct FreeRows {
+    const uint32_t *slot_peer;
+    uint32_t *free_list;
+    uint32_t nkeys;
+    __device__ __forceinline__ uint32_t item(uint64_t pos) const { return slot_peer[pos] == RG_PEER_NONE; }
+    __device__ __forceinline__ void emit(uint64_t pos, uint32_t f, uint32_t ex) const {
+        if (f && ex < nkeys) free_list[ex] = (uint32_t)pos;
+    }
+    __device__ __forceinline__ void total(uint32_t) const {}
+};
 
-__global__ __launch_bounds__(256) void install_rank_kernel(InstallArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t e[kItems], cnt = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        e[k] = base + k < a.n ? a.rank[base + k] : 0u;
-        cnt += e[k];
-    }
-    Count total;
-    uint32_t ex = a.agg_val[blockIdx.x] + block_prefix(Count{0u, cnt}, total).v;
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        if (base + k >= a.n) break;
-        a.rank[base + k] = e[k] ? ex : RG_KEY_SKIP;
-        ex += e[k];
-    }
-}
-
-__global__ __launch_bounds__(256) void free_count_kernel(InstallArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t cnt = 0;
-    for (uint32_t k = 0; k < kItems; ++k)
-        if (base + k < a.t.nkeys) cnt += a.t.slot_peer[base + k] == RG_PEER_NONE;
-    Count total;
-    (void)block_prefix(Count{0u, cnt}, total);
-    if (threadIdx.x == 0) {
-        a.kagg_flag[blockIdx.x] = 0;
-        a.kagg_val[blockIdx.x] = total.v;
-    }
-}
-
-// free_list[k] = the k-th free row, ascending (the entries behind the last stay RG_KEY_SKIP)
-__global__ __launch_bounds__(256) void free_compact_kernel(InstallArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t f[kItems], cnt = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        f[k] = base + k < a.t.nkeys && a.t.slot_peer[base + k] == RG_PEER_NONE;
-        cnt += f[k];
-    }
-    Count total;
-    uint32_t ex = a.kagg_val[blockIdx.x] + block_prefix(Count{0u, cnt}, total).v;
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        if (f[k] && ex < a.t.nkeys) a.free_list[ex] = (uint32_t)(base + k);
-        ex += f[k];
-    }
+// What a row that changes hands holds: the given keys and birth time, no packet sent, none seen.
+__device__ __forceinline__ void reset_row(const Tables &t, uint32_t r, uint4 k0, uint4 k1, uint4 k2, uint4 k3,
+                                          uint64_t born) {
+    t.send_keys[2ull * r] = k0;
+    t.send_keys[2ull * r + 1] = k1;
+    t.recv_keys[2ull * r] = k2;
+    t.recv_keys[2ull * r + 1] = k3;
+    uint64_t *w = t.windows + (uint64_t)kWindowWords * r;
+    for (uint32_t q = 0; q < kWindowWords; ++q) w[q] = 0;
+    uint64_t *s = t.send_state + 3ull * r;
+    s[0] = 0;
+    s[1] = born;
+    s[2] = born;
 }
 
 __global__ __launch_bounds__(256) void install_commit_kernel(InstallArgs a) {
@@ -290,20 +256,10 @@ __global__ __launch_bounds__(256) void install_commit_kernel(InstallArgs a) {
     }
     const uint4 k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3];
     zero_key_row(key);
-    a.t.send_keys[2ull * r] = k0;
-    a.t.send_keys[2ull * r + 1] = k1;
-    a.t.recv_keys[2ull * r] = k2;
-    a.t.recv_keys[2ull * r + 1] = k3;
+    reset_row(a.t, r, k0, k1, k2, k3, a.now_ns ? *a.now_ns : 0);
     a.t.receivers[r] = a.rid[i];
     a.t.local_ids[r] = a.lid[i];
     a.t.slot_peer[r] = peer;
-    uint64_t *w = a.t.windows + (uint64_t)kWindowWords * r;
-    for (uint32_t q = 0; q < kWindowWords; ++q) w[q] = 0;
-    const uint64_t now = a.now_ns ? *a.now_ns : 0;
-    uint64_t *s = a.t.send_state + 3ull * r;
-    s[0] = 0;
-    s[1] = now;
-    s[2] = now;
     atomicMax(&a.claim[peer], i + 1); // peer.current_transport: the last one in array order
     a.rows_out[i] = r;
     a.status[i] = RG_PKT_OK; // after the row
@@ -355,14 +311,7 @@ __global__ __launch_bounds__(256) void expire_kernel(ExpireArgs a) {
     }
     if (gone) {
         const uint4 z = make_uint4(0, 0, 0, 0);
-        a.t.send_keys[2ull * r] = z;
-        a.t.send_keys[2ull * r + 1] = z;
-        a.t.recv_keys[2ull * r] = z;
-        a.t.recv_keys[2ull * r + 1] = z;
-        uint64_t *w = a.t.windows + (uint64_t)kWindowWords * r;
-        for (uint32_t q = 0; q < kWindowWords; ++q) w[q] = 0;
-        uint64_t *s = a.t.send_state + 3ull * r;
-        s[0] = s[1] = s[2] = 0;
+        reset_row(a.t, r, z, z, z, z, 0);
         a.t.receivers[r] = 0;
         a.t.local_ids[r] = 0;
         // only this lane can find r there: a newer session of the peer stays its current one (time.rs:93-95)
@@ -378,16 +327,6 @@ __global__ __launch_bounds__(256) void expire_kernel(ExpireArgs a) {
 using namespace rg::host;
 
 namespace {
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-const dim3 kWg(256);
-
-int bad(const char *what, const char *why) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "%s: %s", what, why);
-    return set_err(RG_EINVAL, buf);
-}
-
 // the struct's rules (include/rg_aead.h); RG_OK with the kernels' view in *out
 int check_tables(const char *what, const rg_session_tables *t, rg::Tables *out) {
     if (!t) return bad(what, "bad args");
@@ -458,10 +397,6 @@ int install(const char *what, rg_ctx *ctx, const rg_session_tables *tables, rg::
     a.ids = reinterpret_cast<unsigned long long *>(ws + L.ids);
     a.ids_mask = L.ids_cap - 1;
     a.ids_shift = 32 - (uint32_t)__builtin_ctzll(L.ids_cap);
-    a.agg_val = words(L.agg_n[0]);
-    a.agg_flag = words(L.agg_n[1]);
-    a.kagg_val = words(L.agg_k[0]);
-    a.kagg_flag = words(L.agg_k[1]);
     a.free_list = words(L.free_list);
     a.claim = words(L.claim);
     a.n = (uint32_t)n;
@@ -469,15 +404,11 @@ int install(const char *what, rg_ctx *ctx, const rg_session_tables *tables, rg::
     RG_HIP(hipMemsetAsync(a.ids, 0xFF, (size_t)L.ids_cap * 8, st), what);
     if (a.t.nkeys) RG_HIP(hipMemsetAsync(a.free_list, 0xFF, (size_t)a.t.nkeys * 4, st), what);
     if (a.t.npeers) RG_HIP(hipMemsetAsync(a.claim, 0, (size_t)a.t.npeers * 4, st), what);
-    const dim3 tiles(L.nblk_n), ktiles(L.nblk_k);
     hipLaunchKernelGGL(rg::install_prep_kernel, lanes(n), kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::install_judge_kernel, tiles, kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::carry_kernel<rg::Count>, dim3(1), kWg, 0, st, a.agg_flag, a.agg_val, L.nblk_n);
-    hipLaunchKernelGGL(rg::install_rank_kernel, tiles, kWg, 0, st, a);
+    rg::compact(rg::InstallJudge{a}, rg::InstallRank{a.rank}, a.n, rg::Agg<uint32_t>(ws, L.agg_n), st);
     if (a.t.nkeys) {
-        hipLaunchKernelGGL(rg::free_count_kernel, ktiles, kWg, 0, st, a);
-        hipLaunchKernelGGL(rg::carry_kernel<rg::Count>, dim3(1), kWg, 0, st, a.kagg_flag, a.kagg_val, L.nblk_k);
-        hipLaunchKernelGGL(rg::free_compact_kernel, ktiles, kWg, 0, st, a);
+        const rg::FreeRows rows{a.t.slot_peer, a.free_list, a.t.nkeys};
+        rg::compact(rows, rows, a.t.nkeys, rg::Agg<uint32_t>(ws, L.agg_k), st);
     }
     hipLaunchKernelGGL(rg::install_commit_kernel, lanes(n), kWg, 0, st, a);
     if (a.t.npeers) hipLaunchKernelGGL(rg::peer_commit_kernel, lanes(a.t.npeers), kWg, 0, st, a);

@@ -14,34 +14,25 @@
 //   clear    one lane per peer: want_ka[p] = want_rk[p] = 0, the lists and the gate all padding, the counts zero
 //   row      one lane per live row: the pending flag and a due entry are taken off the row; what they ask for goes
 //            to want_ka[p] / want_rk[p], the same value from every row of the peer
-//   count    one lane per eight peers: (keepalive, rekey) of each peer, counted per tile of kGroupTile peers, both
-//            counts in one 64-bit sum
-//   carry    rg_grouped.h: the tiles' counts -> what each tile starts from
-//   compact  the same walk again: ka_slots_out[rank] = the peer's current row, rekey_peers_out[rank] = the peer,
-//            rekey_gate_out[rank] = RG_PKT_OK; the last tile stores counts_out
+//   compact  rg_grouped.h's count / carry / rank over the peers, PeerWants in both walks: (keepalive, rekey) of
+//            each peer, both counts in one 64-bit sum; ka_slots_out[rank] = the peer's current row,
+//            rekey_peers_out[rank] = the peer, rekey_gate_out[rank] = RG_PKT_OK; the totals go to counts_out
 // The row kernel writes timers only and the peer kernels read the tables only, so every decision sees the state
 // before the call.
 //
 // The entry points' host side is here too (rg_session.hip's precedent).  All scratch is the caller's; nothing is
 // allocated, waited for or kept in the context.
-#include <cstdio>
-
 #include "rg_host.h"
 #include "rg_grouped.h"
 
 namespace rg {
 namespace {
 
-constexpr uint32_t kItems = kGroupTile / 256; // peers per lane in the scan, consecutive
 constexpr uint64_t kKeepaliveNs = RG_KEEPALIVE_TIMEOUT_NS;
 constexpr uint64_t kRekeyAfterNs = RG_REKEY_AFTER_TIME_NS;
 constexpr uint64_t kRejectAfterNs = RG_REJECT_AFTER_TIME_NS;
 
-struct Sum64 {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
-};
-using Count2 = SegPair<uint64_t, Sum64>; // f stays 0: a plain sum; keepalives in the low word, rekeys in the high
-constexpr uint64_t kOneKa = 1ull, kOneRk = 1ull << 32;
+constexpr uint64_t kOneKa = 1ull, kOneRk = 1ull << 32; // one sum: keepalives in the low word, rekeys in the high
 
 // rg_session_timer as the kernels take it: word 0 rekey_at_ns, word 1 flags (low half) and pad
 __device__ __forceinline__ uint64_t *timer_row(uint64_t *timers, uint32_t r) { return timers + 2ull * r; }
@@ -104,9 +95,6 @@ struct TurnArgs {
     uint32_t nkeys, npeers;
     const uint64_t *now_ns;
     uint32_t *want_ka, *want_rk; // [npeers]
-    uint64_t *agg_val;           // [nblk]
-    uint32_t *agg_flag;          // [nblk]
-    uint32_t nblk;
     uint32_t *ka_slots_out, *rekey_peers_out; // [npeers]
     uint8_t *rekey_gate_out;                  // [npeers]
     uint32_t *counts_out;                     // [2]
@@ -144,79 +132,45 @@ __global__ __launch_bounds__(256) void timer_row_kernel(TurnArgs a) {
     }
 }
 
-// what peer p puts on the two lists: kOneKa and / or kOneRk; *slot = its current row
-__device__ __forceinline__ uint64_t peer_wants(const TurnArgs &a, uint32_t p, uint64_t now, uint32_t *slot) {
-    uint64_t w = a.want_rk[p] ? kOneRk : 0;
-    const uint32_t c = a.peer_slot[p];
-    *slot = c;
-    if (a.want_ka[p] && c < a.nkeys && a.slot_peer[c] == p) {
-        const uint64_t *s = a.send_state + 3ull * c;
-        if (!(s[1] + kRejectAfterNs < now || s[0] >= RG_REJECT_AFTER_MESSAGES)) w |= kOneKa; // should_reject
+// The pass of rg_grouped.h's compact over the peers: what peer p puts on the two lists, kOneKa and / or kOneRk,
+// and where its ranks send it.
+struct PeerWants {
+    TurnArgs a;
+    __device__ __forceinline__ uint64_t item(uint64_t pos) const {
+        const uint32_t p = (uint32_t)pos;
+        uint64_t w = a.want_rk[p] ? kOneRk : 0;
+        const uint32_t c = a.peer_slot[p];
+        if (a.want_ka[p] && c < a.nkeys && a.slot_peer[c] == p) {
+            const uint64_t *s = a.send_state + 3ull * c;
+            if (!(s[1] + kRejectAfterNs < *a.now_ns || s[0] >= RG_REJECT_AFTER_MESSAGES)) w |= kOneKa; // should_reject
+        }
+        return w;
     }
-    return w;
-}
-
-__global__ __launch_bounds__(256) void timer_count_kernel(TurnArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    const uint64_t now = *a.now_ns;
-    uint64_t cnt = 0;
-    for (uint32_t k = 0; k < kItems; ++k) {
-        uint32_t c;
-        if (base + k < a.npeers) cnt += peer_wants(a, (uint32_t)(base + k), now, &c);
-    }
-    Count2 total;
-    (void)block_prefix(Count2{0u, cnt}, total);
-    if (threadIdx.x == 0) {
-        a.agg_flag[blockIdx.x] = 0;
-        a.agg_val[blockIdx.x] = total.v;
-    }
-}
-
-__global__ __launch_bounds__(256) void timer_compact_kernel(TurnArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    const uint64_t now = *a.now_ns;
-    uint64_t w[kItems], cnt = 0;
-    uint32_t c[kItems];
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        c[k] = RG_KEY_SKIP;
-        w[k] = base + k < a.npeers ? peer_wants(a, (uint32_t)(base + k), now, &c[k]) : 0;
-        cnt += w[k];
-    }
-    Count2 total;
-    uint64_t ex = a.agg_val[blockIdx.x] + block_prefix(Count2{0u, cnt}, total).v;
-    const uint64_t all = a.agg_val[blockIdx.x] + total.v; // everything up to this tile's end
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint32_t ka = (uint32_t)ex, rk = (uint32_t)(ex >> 32);
-        if ((w[k] & kOneKa) && ka < a.npeers) a.ka_slots_out[ka] = c[k];
-        if ((w[k] & kOneRk) && rk < a.npeers) {
-            a.rekey_peers_out[rk] = (uint32_t)(base + k);
+    __device__ __forceinline__ void emit(uint64_t pos, uint64_t w, uint64_t ex) const {
+        const uint32_t p = (uint32_t)pos, ka = (uint32_t)ex, rk = (uint32_t)(ex >> 32);
+        if ((w & kOneKa) && ka < a.npeers) a.ka_slots_out[ka] = a.peer_slot[p]; // its current row
+        if ((w & kOneRk) && rk < a.npeers) {
+            a.rekey_peers_out[rk] = p;
             a.rekey_gate_out[rk] = RG_PKT_OK;
         }
-        ex += w[k];
     }
-    if (blockIdx.x == a.nblk - 1 && threadIdx.x == 0) {
+    __device__ __forceinline__ void total(uint64_t all) const {
         a.counts_out[0] = (uint32_t)all;
         a.counts_out[1] = (uint32_t)(all >> 32);
     }
-}
+};
 
 struct TimerLayout {
-    uint64_t want;     // [2][npeers] u32: want_ka, want_rk
-    uint64_t agg_val;  // [nblk] u64
-    uint64_t agg_flag; // [nblk] u32
+    uint64_t want; // [2][npeers] u32: want_ka, want_rk
+    AggLayout agg; // u64 sums of the peers' tiles
     uint64_t total;
-    uint32_t nblk;
 };
 TimerLayout timer_layout(uint64_t nkeys, uint64_t npeers) {
     TimerLayout L{};
     if (nkeys > 0xFFFFFFFFull || npeers > 0xFFFFFFFFull) return L; // total = 0
     WorkspaceCursor ws;
-    L.nblk = (uint32_t)((npeers + kGroupTile - 1) / kGroupTile);
     L.want = ws.take(2 * npeers * 4);
-    L.agg_val = ws.take((uint64_t)L.nblk * 8);
-    L.agg_flag = ws.take((uint64_t)L.nblk * 4);
+    L.agg.take_agg(ws, npeers, 8);
     L.total = ws.total();
     return L;
 }
@@ -227,16 +181,6 @@ TimerLayout timer_layout(uint64_t nkeys, uint64_t npeers) {
 using namespace rg::host;
 
 namespace {
-bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
-const dim3 kWg(256);
-
-int bad(const char *what, const char *why) {
-    char buf[200];
-    snprintf(buf, sizeof buf, "%s: %s", what, why);
-    return set_err(RG_EINVAL, buf);
-}
-
 // the three notes behind their kernels: a carries the kernel's arrays
 template <class Kernel>
 int note(const char *what, Kernel kernel, rg_ctx *ctx, rg_session_timer *timers, rg::NoteArgs a, size_t n,
@@ -329,9 +273,6 @@ extern "C" int rg_timer_turn_dev(rg_ctx *ctx, const rg_session_tables *tables, r
     a.now_ns = now_ns;
     a.want_ka = reinterpret_cast<uint32_t *>(ws + L.want);
     a.want_rk = a.want_ka + a.npeers;
-    a.agg_val = reinterpret_cast<uint64_t *>(ws + L.agg_val);
-    a.agg_flag = reinterpret_cast<uint32_t *>(ws + L.agg_flag);
-    a.nblk = L.nblk;
     a.ka_slots_out = ka_slots_out;
     a.rekey_peers_out = rekey_peers_out;
     a.rekey_gate_out = rekey_gate_out;
@@ -341,11 +282,9 @@ extern "C" int rg_timer_turn_dev(rg_ctx *ctx, const rg_session_tables *tables, r
         RG_HIP(hipGetLastError(), what);
         return RG_OK;
     }
-    const dim3 tiles(L.nblk);
     if (a.nkeys) hipLaunchKernelGGL(rg::timer_row_kernel, lanes(a.nkeys), kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::timer_count_kernel, tiles, kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::carry_kernel<rg::Count2>, dim3(1), kWg, 0, st, a.agg_flag, a.agg_val, L.nblk);
-    hipLaunchKernelGGL(rg::timer_compact_kernel, tiles, kWg, 0, st, a);
+    const rg::PeerWants wants{a};
+    rg::compact(wants, wants, a.npeers, rg::Agg<uint64_t>(ws, L.agg), st);
     RG_HIP(hipGetLastError(), what);
     return RG_OK;
 }

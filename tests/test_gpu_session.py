@@ -163,6 +163,23 @@ def test_install_beyond_one_scan_tile(engine):
     assert want[1].count(sc.FULL) == 5 and want[1].count(sc.OK) == sum(p == sc.NONE for p in t["slot_peer"])
 
 
+@pytest.mark.parametrize("n,nkeys", [(2 * sc.TILE + 3, sc.TILE - 5), (70, 2 * sc.TILE + 3)],
+                         ids=["batch_3_tiles_table_1", "batch_1_tile_table_3"])
+def test_install_batch_and_table_on_different_tile_counts(engine, n, nkeys):
+    """the scan over the batch is bounded by n and the scan over the table by nkeys: three tiles of handshakes into
+    one tile of rows (the free rows run out, most answers RG_PKT_FULL), and one tile of handshakes into three tiles
+    of rows (the free list spans them, every eligible handshake gets a row)"""
+    t = sc.scattered_tables(nkeys, 5, 23)
+    b = sc.scattered_batch(n, 5, 24)
+    T, want = install_vs_model(engine, t, b, 7)
+    status, free = want[1], sum(p == sc.NONE for p in t["slot_peer"])
+    dup = [i for i in range(0, n, 3) if (i // 3) % 4 == 3]  # the id of an earlier row of the batch
+    assert dup and all(status[i] == sc.REJECTED for i in dup)
+    eligible = n - len(range(0, n, 3))
+    assert status.count(sc.OK) == min(free, eligible) > 0 and status.count(sc.FULL) == eligible - min(free, eligible)
+    assert (status.count(sc.FULL) > n // 3) == (n > nkeys)
+
+
 # ------------------------------------------------------------------- expiry
 def test_expiry(engine):
     """started_ns + 180e9 == now stays, one below goes, a started_ns near 2^64 wraps; the list names a live row, a
