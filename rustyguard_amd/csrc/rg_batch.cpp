@@ -226,7 +226,7 @@ int rg_synth_fill_dev(rg_ctx *ctx, const rg_pkt_desc *desc, const uint32_t *inne
 int rg_rx_table_build(const uint32_t *receivers, const uint32_t *key_idx, size_t n, rg_rx_entry *table,
                       uint32_t cap) {
     if (!table || (n && (!receivers || !key_idx))) return set_err(RG_EINVAL, "rx table: null pointer");
-    if (cap == 0 || (cap & (cap - 1)) != 0 || (uint64_t)cap < 2ull * n)
+    if (!pow2(cap) || (uint64_t)cap < 2ull * n)
         return set_err(RG_EINVAL, "rx table: cap must be a power of two >= 2 n");
     for (uint32_t s = 0; s < cap; ++s) table[s] = rg_rx_entry{0, RG_KEY_SKIP};
     for (size_t i = 0; i < n; ++i) {
@@ -242,7 +242,7 @@ int rg_rx_table_build(const uint32_t *receivers, const uint32_t *key_idx, size_t
 }
 
 int64_t rg_rx_table_find(const rg_rx_entry *table, uint32_t cap, uint32_t receiver) {
-    if (!table || cap == 0 || (cap & (cap - 1)) != 0) return -1;
+    if (!table || !pow2(cap)) return -1;
     const uint32_t k = rg::rx_find(table, cap, receiver);
     return k == RG_KEY_SKIP ? -1 : (int64_t)k;
 }
@@ -261,7 +261,7 @@ static uint32_t peer_key_word(const uint8_t *pk) {
 
 int rg_peer_table_build(const rg_hs_peer *peers, uint32_t npeers, uint32_t *table, uint32_t cap) {
     if (!table || (npeers && !peers)) return set_err(RG_EINVAL, "peer table: null pointer");
-    if (cap == 0 || (cap & (cap - 1)) != 0 || (uint64_t)cap < 2ull * npeers)
+    if (!pow2(cap) || (uint64_t)cap < 2ull * npeers)
         return set_err(RG_EINVAL, "peer table: cap must be a power of two >= 2 npeers");
     for (uint32_t s = 0; s < cap; ++s) table[s] = RG_PEER_NONE;
     for (uint32_t i = 0; i < npeers; ++i) {
@@ -277,7 +277,7 @@ int rg_peer_table_build(const rg_hs_peer *peers, uint32_t npeers, uint32_t *tabl
 }
 
 int64_t rg_peer_table_find(const rg_hs_peer *peers, const uint32_t *table, uint32_t cap, const uint8_t pk[32]) {
-    if (!peers || !table || !pk || cap == 0 || (cap & (cap - 1)) != 0) return -1;
+    if (!peers || !table || !pk || !pow2(cap)) return -1;
     uint32_t s = rg::rx_slot(peer_key_word(pk), cap);
     for (uint32_t probe = 0; probe < cap && table[s] != RG_PEER_NONE; ++probe) {
         if (peer_key_diff(peers[table[s]].public_key, pk) == 0) return table[s];
@@ -293,7 +293,7 @@ int rg_open_batch_dev_rx(rg_ctx *ctx, const uint8_t *keys, uint32_t nkeys, const
     int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
-    if (!rx_table || rx_cap == 0 || (rx_cap & (rx_cap - 1)) != 0 || !desc || n > 0xFFFFFFFFull)
+    if (!rx_table || !pow2(rx_cap) || !desc || n > 0xFFFFFFFFull)
         return set_err(RG_EINVAL, "open_rx: bad args");
     rc = claim_stream(ctx, (hipStream_t)stream); // before the resolve pass writes the context's descriptors
     if (rc) return rc;

@@ -20,14 +20,11 @@
 // launch), on rg_host.h like the host units: those are also linked against a
 // CPU stand-in of the launchers (tests/sanitize) and so name no launcher of
 // this file.
-#include "rg_blake2s.h"
-#include "rg_device.h"
 #include "rg_host.h"
+#include "rg_noise.h"
 
 namespace rg {
 namespace {
-
-constexpr uint32_t kInitLen = 148, kRespLen = 92; // HandshakeInit / HandshakeResp (rustyguard-types)
 
 struct CookieArgs {
     const uint32_t *keys;    // rg_cookie_keys as LE words: [0, 8) mac1_key, [8, 16) cookie_key, [16, 24) secret
@@ -64,12 +61,8 @@ __global__ __launch_bounds__(256) void cookie_reply_kernel(CookieArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
     const rg_pkt_desc d = a.desc[i];
-    uint8_t st;
-    if ((d.offset & 15u) != 0) st = RG_PKT_UNALIGNED;
-    else if (d.offset > a.buf_len || d.len > a.buf_len - d.offset || (d.len != kInitLen && d.len != kRespLen))
-        st = RG_PKT_INVALID;
-    else if (d.key_idx == RG_KEY_SKIP) st = RG_PKT_REJECTED;
-    else {
+    uint32_t st = frame_verdict(d, RG_PKT_OK, a.buf_len, kInitLen, kRespLen); // no gate
+    if (st == kGoing) {
         const uint8_t *msg = a.buf + d.offset;
         const uint4 head = *reinterpret_cast<const uint4 *>(msg); // type, sender, ...
         if (head.x != (d.len == kInitLen ? 1u : 2u)) st = RG_PKT_INVALID; // Error::InvalidMessage
@@ -90,28 +83,16 @@ __global__ __launch_bounds__(256) void cookie_reply_kernel(CookieArgs a) {
 #pragma unroll
                 for (int w = 0; w < 8; ++w) h[w] = s_ks[1][w];
                 b2s_compress(h, m, 64 + 18, true);
-                const uint32_t cookie[4] = {h[0], h[1], h[2], h[3]};
-                b2s_key_state(cookie, 16, false, ks);
+                const uint4 cookie = make_uint4(h[0], h[1], h[2], h[3]);
+                b2s_key_state(h, 16, false, ks); // keyed by the cookie: the digest's first 16 bytes
                 if (mac_diff(b2s_mac16(ks, msg, d.len - 16), mac_field(msg, d.len - 16)) == 0) st = RG_PKT_OK;
                 else {
                     // write_cookie_message: encrypt_cookie(cookie, cookie_key, nonce, aad = mac1)
                     const uint2 *np = reinterpret_cast<const uint2 *>(a.nonces + 24ull * i);
                     const uint2 n0 = np[0], n1 = np[1], n2 = np[2];
-                    const uint32_t hn[4] = {n0.x, n0.y, n1.x, n1.y};
-                    const Key8 sub = hchacha20(load_key(a.keys, 1), hn);
-                    uint32_t otk[16], stream[16];
-                    chacha_block(sub, 0, 0, n2.x, n2.y, otk); // one-time Poly1305 key
-                    chacha_block(sub, 1, 0, n2.x, n2.y, stream);
-                    const uint4 ct = make_uint4(cookie[0] ^ stream[0], cookie[1] ^ stream[1], cookie[2] ^ stream[2],
-                                                cookie[3] ^ stream[3]);
-                    const Mul r = make_mul(otk[0], otk[1], otk[2], otk[3]);
-                    Acc acc = {0, 0, 0, 0, 0};
-                    acc_block(acc, mac1, r);      // AAD: 16 bytes, no padding
-                    acc_block(acc, ct, r);        // ciphertext: 16 bytes
-                    acc_add(acc, 16, 0, 16, 0, 1); // le64(aad_len) || le64(ct_len)
-                    acc_mul(acc, r);
+                    const uint32_t nonce[6] = {n0.x, n0.y, n1.x, n1.y, n2.x, n2.y};
                     uint32_t tag[4];
-                    acc_finish(acc, otk[4], otk[5], otk[6], otk[7], tag);
+                    const uint4 ct = cookie_aead(load_key(a.keys, 1), nonce, mac1, cookie, true, tag);
                     // CookieMessage {type = 3, receiver = the message's sender, nonce, cookie, tag}
                     uint4 *out = reinterpret_cast<uint4 *>(a.replies + 64ull * i);
                     out[0] = make_uint4(3u, head.y, n0.x, n0.y);
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(256) void cookie_reply_kernel(CookieArgs a) {
             }
         }
     }
-    a.status[i] = st;
+    a.status[i] = (uint8_t)st;
 }
 
 } // namespace
@@ -139,11 +120,11 @@ extern "C" int rg_cookie_reply_batch_dev(rg_ctx *ctx, const rg_cookie_keys *keys
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!keys || !desc || !addrs || !nonces || !buf || !replies || !status || n > 0xFFFFFFFFull)
-        return set_err(RG_EINVAL, "cookie reply: bad args");
+        return bad("cookie reply", "bad args");
     if (misaligned(keys, 16) || misaligned(replies, 16))
-        return set_err(RG_EINVAL, "cookie reply: keys and replies must be 16-byte aligned");
+        return bad("cookie reply", "keys and replies must be 16-byte aligned");
     if (misaligned(addrs, 8) || misaligned(nonces, 8))
-        return set_err(RG_EINVAL, "cookie reply: addrs and nonces must be 8-byte aligned");
+        return bad("cookie reply", "addrs and nonces must be 8-byte aligned");
     rg::CookieArgs a{};
     a.keys = reinterpret_cast<const uint32_t *>(keys);
     a.desc = desc;

@@ -13,69 +13,35 @@
 //   handshake_commit_kernel    the verdict of the finish: the lowest claiming message of a pending row gets
 //                              RG_PKT_OK and wipes the row (hs.zeroize()), every other claimant is rejected
 //
+// What lives where: this file holds each kernel's line of the Noise pattern (which token follows which, under
+// which keys), the layout of its messages and rows, and the entry points' host side (on rg_host.h, like
+// rg_cookie.hip's).  rg_noise.h holds what the lines are made of: the symmetric state (Noise: mix_hash,
+// mix_chain, mix_key, mix_key_and_hash, split, encrypt_and_hash, decrypt_and_hash), the fields' AEAD, mac1 and
+// mac2, the frame preamble and the row helpers.  rg_blake2s.h holds the hash, HMAC and HKDF under them, and
+// rg_x25519.h the ladder.
+//
 // The cost is the X25519 ladder of rg_x25519.h: two per initiation consumed, three per response built, three
 // per initiation built, two per response consumed, ~2800 field multiplications each; everything else (some
-// fifty BLAKE2s compressions, a few ChaCha20 blocks) is noise beside it.  So the kernels are laid out for code size, not for the hash: the ladders of one kernel share
-// one call site (a loop over the kernel's Diffie-Hellman steps, with the work that follows each step chosen
-// by the loop count, which is public), and the HKDF steps share b2s_hkdf's.  Workgroups are one wave, so that
-// a batch of a thousand messages still spreads over sixteen CUs.
+// fifty BLAKE2s compressions, a few ChaCha20 blocks) is noise beside it.  So the kernels are laid out for code
+// size, not for the hash: the ladders of one kernel share one call site (a `#pragma unroll 1` loop over the
+// kernel's Diffie-Hellman steps, with the work that follows each step chosen by the loop count, which is
+// public; a step that failed falls through the rest of the loop, which has a single exit), and the HKDF steps
+// share b2s_hkdf's.  Workgroups are one wave, so that a batch of a thousand messages still spreads over
+// sixteen CUs.
 //
 // Constant time: no branch and no address depends on a private key, a shared secret, a chaining key or an
 // AEAD key.  Branches follow the descriptor, the gate, the loop counts and the verdicts that the status array
 // publishes anyway (a zero shared secret, a failed tag, an unknown static key); tag and key comparisons are
 // OR-folds over all their words.  Nothing derived from a key is written to global memory except the rows
 // the interface defines, and a row whose message fails is written as zeros.
-//
-// The entry points' host side is here too, on rg_host.h, like rg_cookie.hip's.
-#include "rg_blake2s.h"
-#include "rg_device.h"
 #include "rg_host.h"
+#include "rg_noise.h"
 #include "rg_x25519.h"
 
 namespace rg {
 namespace {
 
-constexpr int kHsWG = 64;           // one wave per workgroup
-constexpr uint32_t kGoing = 0xFFu;  // no verdict yet (never stored)
-constexpr uint32_t kInitLen = 148;  // HandshakeInit (rustyguard-types)
-
-// HandshakeState::default(): BLAKE2s("Noise_IKpsk2_25519_ChaChaPoly_BLAKE2s") and
-// BLAKE2s(that || "WireGuard v1 zx2c4 Jason@zx2c4.com"), as little-endian words
-__device__ constexpr uint32_t kConstruction[8] = {0xAE6DE260u, 0xC0EF27F3u, 0xE235C32Eu, 0xD0D225A0u,
-                                                  0x0642EB16u, 0xF57772F8u, 0x98D1382Du, 0x36CD788Bu};
-__device__ constexpr uint32_t kIdentifier[8] = {0x61B31122u, 0x66C51A08u, 0xDB431269u, 0x32D58A45u,
-                                                0x666C9C2Du, 0xB7E89322u, 0x659CE10Eu, 0xF39E07BAu};
-
-__device__ __forceinline__ void load8(const uint32_t *p, uint32_t w[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = p[i];
-}
-
-// ChaCha20-Poly1305 with nonce 0 and aad = the 32-byte transcript hash over a payload of at most two
-// 16-byte blocks (Encrypted<N>, prim.rs:330-366; N = 32, 12 or 0): the tag over ciphertext ct (zero past
-// len bytes) and the keystream of block 1.  seal: ct holds the plaintext (zero past len bytes) and is
-// encrypted in place first.
-__device__ __forceinline__ void hs_aead(const uint32_t key[8], const uint32_t aad[8], uint32_t ct[8], uint32_t len,
-                                        uint32_t stream[16], uint32_t tag[4], bool seal = false) {
-    Key8 k;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) k.k[i] = key[i];
-    uint32_t otk[16];
-    chacha_block(k, 0, 0, 0, 0, otk);
-    chacha_block(k, 1, 0, 0, 0, stream);
-    if (seal) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ct[i] = (uint32_t)(4 * i) < len ? ct[i] ^ stream[i] : 0u;
-    }
-    const Mul r = make_mul(otk[0], otk[1], otk[2], otk[3]);
-    Acc acc = {0, 0, 0, 0, 0};
-    acc_block(acc, make_uint4(aad[0], aad[1], aad[2], aad[3]), r);
-    acc_block(acc, make_uint4(aad[4], aad[5], aad[6], aad[7]), r);
-    acc_block_pred(acc, make_uint4(ct[0], ct[1], ct[2], ct[3]), r, len > 0);
-    acc_block_pred(acc, make_uint4(ct[4], ct[5], ct[6], ct[7]), r, len > 16);
-    acc_block(acc, make_uint4(32u, 0u, len, 0u), r); // le64(aad_len) || le64(ct_len)
-    acc_finish(acc, otk[4], otk[5], otk[6], otk[7], tag);
-}
+constexpr int kHsWG = 64; // one wave per workgroup
 
 // ------------------------------------------------------------------ X25519
 struct X25519Args {
@@ -114,82 +80,66 @@ struct HsInitArgs {
     uint32_t n;
 };
 
+// -> e, es, s, ss, {timestamp}, read
 __global__ __launch_bounds__(kHsWG) void handshake_init_kernel(HsInitArgs a) {
     __shared__ uint32_t s_hash[8]; // the transcript hash after mix_hash(own public key): the same for every message
     if (threadIdx.x == 0) {
-        uint32_t pk[12] = {}, h[8];
+        uint32_t chain[8], hash[8], pk[12] = {};
+        Noise ns{chain, hash};
         load8(a.own + 8, pk);
-        b2s_hash32(kIdentifier, pk, 8, h);
+        ns.init();
+        ns.mix_hash(pk, 8);
 #pragma unroll
-        for (int w = 0; w < 8; ++w) s_hash[w] = h[w];
+        for (int w = 0; w < 8; ++w) s_hash[w] = ns.hash[w];
     }
     __syncthreads();
     const uint32_t i = blockIdx.x * kHsWG + threadIdx.x;
     if (i >= a.n) return;
     const rg_pkt_desc d = a.desc[i];
-    uint32_t st = kGoing;
-    if ((d.offset & 15u) != 0) st = RG_PKT_UNALIGNED;
-    else if (d.offset > a.buf_len || d.len > a.buf_len - d.offset || d.len != kInitLen) st = RG_PKT_INVALID;
-    else if ((a.gate && a.gate[i] != RG_PKT_OK) || d.key_idx == RG_KEY_SKIP) st = RG_PKT_REJECTED;
+    uint32_t st = frame_verdict(d, a.gate ? a.gate[i] : (uint32_t)RG_PKT_OK, a.buf_len, kInitLen);
 
     uint32_t m[32] = {}; // the message's first 128 bytes: type, sender, ephemeral 2..10, static 10..22, timestamp 22..29
-    uint32_t chain[8], hash[8], point[8], spk[8] = {}, ts[3] = {};
+    uint32_t chain[8] = {}, hash[8] = {};
+    Noise ns{chain, hash};
+    uint32_t point[8], spk[8] = {}, ts[3] = {};
     uint32_t peer = RG_PEER_NONE;
     if (st == kGoing) {
-        const uint4 *mp = reinterpret_cast<const uint4 *>(a.buf + d.offset);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const uint4 v = mp[q];
-            m[4 * q] = v.x; m[4 * q + 1] = v.y; m[4 * q + 2] = v.z; m[4 * q + 3] = v.w;
-        }
+        load_words<32>(reinterpret_cast<const uint4 *>(a.buf + d.offset), m);
         if (m[0] != 1u) st = RG_PKT_INVALID; // Error::InvalidMessage
     }
     if (st == kGoing) {
-        // -> e: mix_hash(ephemeral), mix_chain(ephemeral)
-        uint32_t e[12] = {}, h0[8], none[8];
+        // -> e
+        uint32_t e[12] = {}, sk[8];
+        ns.init();
 #pragma unroll
         for (int w = 0; w < 8; ++w) {
             e[w] = point[w] = m[2 + w];
-            h0[w] = s_hash[w];
-            chain[w] = kConstruction[w];
+            ns.hash[w] = s_hash[w];
         }
-        b2s_hash32(h0, e, 8, hash);
-        b2s_hkdf(chain, e, 32, 0, none, none);
-        uint32_t sk[8];
+        ns.mix_hash(e, 8);
+        ns.mix_chain(e);
         load8(a.own, sk);
         // -> es, s (step 0: the ephemeral key, the encrypted static key) and -> ss, payload (step 1: the
         // decrypted static key, the encrypted timestamp)
 #pragma unroll 1
         for (int step = 0; step < 2; ++step) {
             if (st != kGoing) continue; // a step that failed ends the message (no break: single-exit loop)
-            uint32_t dh[8], key[8], none2[8];
+            uint32_t dh[8], key[8], f[12], pt[8];
             if (x25519_words(sk, point, dh) == 0) {
                 st = RG_PKT_KEYEXCHANGE;
                 continue;
             }
-            b2s_hkdf(chain, dh, 32, 1, key, none2); // mix_key
-            uint32_t f[12], ct[8], stream[16], tag[4];
+            ns.mix_key(dh, key);
 #pragma unroll
             for (int w = 0; w < 12; ++w) f[w] = step ? (w < 7 ? m[22 + w] : 0u) : m[10 + w]; // ciphertext || tag
-            const uint32_t len = step ? 12u : 32u;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) ct[w] = (uint32_t)(4 * w) < len ? f[w] : 0u;
-            hs_aead(key, hash, ct, len, stream, tag);
-            uint32_t diff = 0; // the field's tag follows its 3 or 8 ciphertext words
-#pragma unroll
-            for (int w = 0; w < 4; ++w) diff |= tag[w] ^ (step ? f[3 + w] : f[8 + w]);
-            if (diff != 0) {
+            if (!ns.decrypt_and_hash(key, f, step ? 12u : 32u, pt)) {
                 st = RG_PKT_DECRYPT_ERR;
                 continue;
             }
-            uint32_t nh[8];
-            b2s_hash32(hash, f, step ? 7u : 12u, nh); // mix_hash(ciphertext || tag)
 #pragma unroll
             for (int w = 0; w < 8; ++w) {
-                hash[w] = nh[w];
-                const uint32_t pt = ct[w] ^ stream[w];
-                if (step == 0) spk[w] = point[w] = pt;
-                else if (w < 3) ts[w] = pt;
+                if (step == 0) spk[w] = point[w] = pt[w];
+                else if (w < 3) ts[w] = pt[w];
             }
         }
     }
@@ -216,14 +166,11 @@ __global__ __launch_bounds__(kHsWG) void handshake_init_kernel(HsInitArgs a) {
     }
     const bool ok = st == RG_PKT_OK;
     uint4 *row = a.results + 8ull * i;
-    row[0] = ok ? make_uint4(chain[0], chain[1], chain[2], chain[3]) : make_uint4(0, 0, 0, 0);
-    row[1] = ok ? make_uint4(chain[4], chain[5], chain[6], chain[7]) : make_uint4(0, 0, 0, 0);
-    row[2] = ok ? make_uint4(hash[0], hash[1], hash[2], hash[3]) : make_uint4(0, 0, 0, 0);
-    row[3] = ok ? make_uint4(hash[4], hash[5], hash[6], hash[7]) : make_uint4(0, 0, 0, 0);
-    row[4] = ok ? make_uint4(m[2], m[3], m[4], m[5]) : make_uint4(0, 0, 0, 0);
-    row[5] = ok ? make_uint4(m[6], m[7], m[8], m[9]) : make_uint4(0, 0, 0, 0);
+    store_or_zero(row, ns.chain, 2, ok);
+    store_or_zero(row + 2, ns.hash, 2, ok);
+    store_or_zero(row + 4, m + 2, 2, ok); // the initiator's ephemeral key
     row[6] = ok ? make_uint4(ts[0], ts[1], ts[2], peer) : make_uint4(0, 0, 0, RG_PEER_NONE);
-    row[7] = ok ? make_uint4(m[1], 0, 0, 0) : make_uint4(0, 0, 0, 0);
+    row[7] = make_uint4(ok ? m[1] : 0u, 0, 0, 0);
     a.status[i] = (uint8_t)st; // after the row
 }
 
@@ -243,6 +190,7 @@ struct HsRespArgs {
     uint32_t n;
 };
 
+// <- e, ee, se, psk, {}, written; split(false)
 __global__ __launch_bounds__(kHsWG) void handshake_resp_kernel(HsRespArgs a) {
     const uint32_t i = blockIdx.x * kHsWG + threadIdx.x;
     if (i >= a.n) return;
@@ -251,24 +199,20 @@ __global__ __launch_bounds__(kHsWG) void handshake_resp_kernel(HsRespArgs a) {
         return;
     }
     uint4 *row = a.results + 8ull * i;
-    uint32_t chain[8], hash[8], eph[8], epk_r[8] = {}, w[24] = {}, send[8] = {};
-    {
-        const uint4 r0 = row[0], r1 = row[1], r2 = row[2], r3 = row[3], r4 = row[4], r5 = row[5];
-        chain[0] = r0.x; chain[1] = r0.y; chain[2] = r0.z; chain[3] = r0.w;
-        chain[4] = r1.x; chain[5] = r1.y; chain[6] = r1.z; chain[7] = r1.w;
-        hash[0] = r2.x; hash[1] = r2.y; hash[2] = r2.z; hash[3] = r2.w;
-        hash[4] = r3.x; hash[5] = r3.y; hash[6] = r3.z; hash[7] = r3.w;
-        eph[0] = r4.x; eph[1] = r4.y; eph[2] = r4.z; eph[3] = r4.w;
-        eph[4] = r5.x; eph[5] = r5.y; eph[6] = r5.z; eph[7] = r5.w;
-    }
+    uint32_t chain[8], hash[8];
+    Noise ns{chain, hash};
+    uint32_t eph[8], epk_r[8] = {}, w[24] = {}, send[8] = {};
+    load_words<8>(row, ns.chain);
+    load_words<8>(row + 2, ns.hash);
+    load_words<8>(row + 4, eph);
     const uint32_t peer = row[6].w, sender = row[7].x;
     uint32_t st = peer < a.npeers ? kGoing : (uint32_t)RG_PKT_INVALID;
     if (st == kGoing) {
         const uint32_t *pr = a.peers + 24ull * peer; // public key, preshared key, mac1 key
-        uint32_t esk[8], spk[8], none[8];
+        uint32_t esk[8], spk[8];
         load8(a.esk + 8ull * i, esk);
         load8(pr, spk);
-        // <- e (step 0: the base point; mix_chain and mix_hash of our ephemeral public key), ee (step 1),
+        // <- e (step 0: the base point; our ephemeral public key goes into the chain and the hash), ee (step 1),
         // se (step 2): every step ends in mix_chain of the ladder's output
 #pragma unroll 1
         for (int step = 0; step < 3; ++step) {
@@ -280,25 +224,21 @@ __global__ __launch_bounds__(kHsWG) void handshake_resp_kernel(HsRespArgs a) {
                 st = RG_PKT_KEYEXCHANGE;
                 continue;
             }
-            b2s_hkdf(chain, out, 32, 0, none, none);
+            ns.mix_chain(out);
             if (step == 0) {
-                uint32_t nh[8];
-                b2s_hash32(hash, out, 8, nh);
+                ns.mix_hash(out, 8);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    hash[q] = nh[q];
-                    epk_r[q] = out[q];
-                }
+                for (int q = 0; q < 8; ++q) epk_r[q] = out[q];
             }
         }
         if (st == kGoing) {
-            // <- psk: mix_key_and_hash; payload: the empty AEAD under aad = hash
-            uint32_t psk[8], t[12] = {}, key[8], nh[8], zero[8] = {}, stream[16], tag[4];
+            // <- psk, then the empty payload
+            uint32_t psk[8], key[8], tag[4];
             load8(pr + 8, psk);
-            b2s_hkdf(chain, psk, 32, 2, t, key);
-            b2s_hash32(hash, t, 8, nh);
-            hs_aead(key, nh, zero, 0, stream, tag);
-            // HandshakeResp: type, sender = our session id, receiver = the initiation's sender, ephemeral, empty
+            ns.mix_key_and_hash(psk, key);
+            ns.empty_tag(key, tag);
+            // HandshakeResp: type, sender = our session id, receiver = the initiation's sender, ephemeral 3..11,
+            // empty 11..15, mac1 15..19, mac2 19..23
             w[0] = 2u;
             w[1] = a.session_ids[i];
             w[2] = sender;
@@ -306,44 +246,16 @@ __global__ __launch_bounds__(kHsWG) void handshake_resp_kernel(HsRespArgs a) {
             for (int q = 0; q < 8; ++q) w[3 + q] = epk_r[q];
 #pragma unroll
             for (int q = 0; q < 4; ++q) w[11 + q] = tag[q];
-            // mac1 = BLAKE2s-128(mac1_key, bytes 0..60)
-            uint32_t ks[8], mk[8], blk[16];
-            load8(pr + 16, mk);
-            b2s_key_state(mk, 32, false, ks);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) blk[q] = q < 15 ? w[q] : 0u;
-            b2s_compress(ks, blk, 64 + 60, true);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[15 + q] = ks[q];
-            // mac2 = BLAKE2s-128(cookie, bytes 0..76) when the peer gave us a cookie, else zero
-            if (a.cookies && a.has_cookie[i] != 0) {
-                uint32_t ck[8] = {};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) ck[q] = a.cookies[4ull * i + q];
-                b2s_key_state(ck, 16, false, ks);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) blk[q] = w[q];
-                b2s_compress(ks, blk, 128, false);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) blk[q] = q < 3 ? w[16 + q] : 0u;
-                b2s_compress(ks, blk, 64 + 76, true);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[19 + q] = ks[q];
-            }
-            // split(false): send under HKDF's second output, receive under the new chain
-            b2s_hkdf(chain, zero, 0, 1, send, none);
+            hs_macs<23>(w, pr + 16, a.cookies && a.has_cookie[i] != 0 ? a.cookies + 4ull * i : nullptr);
+            ns.split(send); // split(false): send under HKDF's second output, receive under the new chain
             st = RG_PKT_OK;
         }
     }
     const bool ok = st == RG_PKT_OK;
-    uint4 *resp = a.responses + 6ull * i, *tk = a.tkeys + 4ull * i;
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-        resp[q] = ok ? make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]) : make_uint4(0, 0, 0, 0);
-    tk[0] = ok ? make_uint4(send[0], send[1], send[2], send[3]) : make_uint4(0, 0, 0, 0);
-    tk[1] = ok ? make_uint4(send[4], send[5], send[6], send[7]) : make_uint4(0, 0, 0, 0);
-    tk[2] = ok ? make_uint4(chain[0], chain[1], chain[2], chain[3]) : make_uint4(0, 0, 0, 0);
-    tk[3] = ok ? make_uint4(chain[4], chain[5], chain[6], chain[7]) : make_uint4(0, 0, 0, 0);
+    uint4 *tk = a.tkeys + 4ull * i;
+    store_or_zero(a.responses + 6ull * i, w, 6, ok);
+    store_or_zero(tk, send, 2, ok);
+    store_or_zero(tk + 2, ns.chain, 2, ok);
     // HandshakeState::zeroize: the row's chaining key and hash are consumed, whatever the verdict
 #pragma unroll
     for (int q = 0; q < 4; ++q) row[q] = make_uint4(0, 0, 0, 0);
@@ -351,23 +263,6 @@ __global__ __launch_bounds__(kHsWG) void handshake_resp_kernel(HsRespArgs a) {
 }
 
 // --------------------------------------------------------------- initiate
-// BLAKE2s-128(key, the first NW words of w): mac1 under a 32-byte key, mac2 under a 16-byte cookie
-// (HasMac, lib.rs:114-209), as handshake_resp_kernel computes them
-template <int NW>
-__device__ __forceinline__ void hs_mac(const uint32_t key[8], uint32_t key_len, const uint32_t *w, uint32_t out[4]) {
-    uint32_t ks[8], blk[16];
-    b2s_key_state(key, key_len, false, ks);
-#pragma unroll
-    for (int b = 0; 16 * b < NW; ++b) {
-        const bool last = 16 * (b + 1) >= NW;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) blk[q] = 16 * b + q < NW ? w[16 * b + q] : 0u;
-        b2s_compress(ks, blk, 64 + (last ? 4 * NW : 64 * (b + 1)), last);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = ks[q];
-}
-
 struct HsInitiateArgs {
     const uint32_t *own;   // rg_hs_static
     const uint32_t *peers; // [npeers] rg_hs_peer rows of 24 words
@@ -385,6 +280,7 @@ struct HsInitiateArgs {
     uint32_t n;
 };
 
+// -> e, es, s, ss, {timestamp}, written
 __global__ __launch_bounds__(kHsWG) void handshake_initiate_kernel(HsInitiateArgs a) {
     const uint32_t i = blockIdx.x * kHsWG + threadIdx.x;
     if (i >= a.n) return;
@@ -395,7 +291,9 @@ __global__ __launch_bounds__(kHsWG) void handshake_initiate_kernel(HsInitiateArg
     const uint32_t peer = a.peer_idx[i];
     uint32_t st = peer < a.npeers ? kGoing : (uint32_t)RG_PKT_INVALID;
     // the message: type, sender, ephemeral 2..10, static 10..22, timestamp 22..29, mac1 29..33, mac2 33..37
-    uint32_t chain[8] = {}, hash[8] = {}, esk[8] = {}, w[40] = {};
+    uint32_t chain[8] = {}, hash[8] = {};
+    Noise ns{chain, hash};
+    uint32_t esk[8] = {}, w[40] = {};
     if (st == kGoing) {
         const uint32_t *pr = a.peers + 24ull * peer; // public key, preshared key, mac1 key
         uint32_t sk[8], pk[8], spk[12] = {}, ts[3];
@@ -405,83 +303,49 @@ __global__ __launch_bounds__(kHsWG) void handshake_initiate_kernel(HsInitiateArg
         load8(pr, spk);
 #pragma unroll
         for (int q = 0; q < 3; ++q) ts[q] = a.ts[3ull * i + q];
-        // HandshakeState::default() and mix_hash(the responder's static public key)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) chain[q] = kConstruction[q];
-        b2s_hash32(kIdentifier, spk, 8, hash);
+        ns.init();
+        ns.mix_hash(spk, 8); // the responder's static public key
         w[0] = 1u;
         w[1] = a.session_ids[i];
-        // -> e (step 0: the base point; mix_hash and mix_chain of our ephemeral public key), es and s (step 1:
-        // mix_key, the sealed static key), ss and the payload (step 2: mix_key, the sealed timestamp); every
-        // step ends in mix_hash of what it put into the message
+        // -> e (step 0: the base point; no key yet, so our ephemeral public key goes in the clear), es and s
+        // (step 1: the sealed static key), ss and the payload (step 2: the sealed timestamp): every step mixes
+        // its ladder's output into the chain and ends in mix_hash of what it put into the message
 #pragma unroll 1
         for (int step = 0; step < 3; ++step) {
-            uint32_t scalar[8], point[8], out[12] = {};
+            uint32_t scalar[8], point[8], dh[8];
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 scalar[q] = step == 2 ? sk[q] : esk[q];
                 point[q] = step == 0 ? (q == 0 ? 9u : 0u) : spk[q];
             }
             if (st != kGoing) continue; // a step that failed ends the row (no break: single-exit loop)
-            if (x25519_words(scalar, point, out) == 0) { // never for the base point
+            if (x25519_words(scalar, point, dh) == 0) { // never for the base point
                 st = RG_PKT_KEYEXCHANGE;
                 continue;
             }
-            uint32_t key[8], none[8], nh[8];
-            b2s_hkdf(chain, out, 32, step ? 1 : 0, key, none);
-            if (step == 0) {
+            uint32_t key[8], field[8], out[12];
+            ns.mix_key(dh, key, step != 0);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) w[2 + q] = out[q];
-            } else {
-                uint32_t ct[8], stream[16], tag[4];
+            for (int q = 0; q < 8; ++q) field[q] = step == 0 ? dh[q] : step == 1 ? pk[q] : (q < 3 ? ts[q] : 0u);
+            ns.encrypt_and_hash(key, step != 0, field, step == 2 ? 12u : 32u, out);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) ct[q] = step == 1 ? pk[q] : (q < 3 ? ts[q] : 0u);
-                hs_aead(key, hash, ct, step == 1 ? 32u : 12u, stream, tag, true);
-#pragma unroll
-                for (int q = 0; q < 12; ++q) // ciphertext || tag: 12 words of the static field, 7 of the timestamp
-                    out[q] = step == 1 ? (q < 8 ? ct[q] : tag[q - 8]) : (q < 3 ? ct[q] : q < 7 ? tag[q - 3] : 0u);
-                if (step == 1) {
-#pragma unroll
-                    for (int q = 0; q < 12; ++q) w[10 + q] = out[q];
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 7; ++q) w[22 + q] = out[q];
-                }
+            for (int q = 0; q < 12; ++q) { // 8 words of the ephemeral key, 12 of the static field, 7 of the timestamp
+                if (step == 0 && q < 8) w[2 + q] = out[q];
+                if (step == 1) w[10 + q] = out[q];
+                if (step == 2 && q < 7) w[22 + q] = out[q];
             }
-            b2s_hash32(hash, out, step == 0 ? 8u : step == 1 ? 12u : 7u, nh);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) hash[q] = nh[q];
         }
         if (st == kGoing) {
-            // mac1 = BLAKE2s-128(mac1_key, bytes 0..116); mac2 = BLAKE2s-128(cookie, bytes 0..132) when the peer
-            // gave us a cookie, else zero
-            uint32_t mk[8], m[4];
-            load8(pr + 16, mk);
-            hs_mac<29>(mk, 32, w, m);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[29 + q] = m[q];
-            if (a.cookies && a.has_cookie[i] != 0) {
-                uint32_t ck[8] = {};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) ck[q] = a.cookies[4ull * i + q];
-                hs_mac<33>(ck, 16, w, m);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[33 + q] = m[q];
-            }
+            hs_macs<37>(w, pr + 16, a.cookies && a.has_cookie[i] != 0 ? a.cookies + 4ull * i : nullptr);
             st = RG_PKT_OK;
         }
     }
     const bool ok = st == RG_PKT_OK;
-    uint4 *msg = a.messages + 10ull * i, *pend = a.pending + 8ull * i;
-#pragma unroll
-    for (int q = 0; q < 10; ++q)
-        msg[q] = ok ? make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]) : make_uint4(0, 0, 0, 0);
-    pend[0] = ok ? make_uint4(chain[0], chain[1], chain[2], chain[3]) : make_uint4(0, 0, 0, 0);
-    pend[1] = ok ? make_uint4(chain[4], chain[5], chain[6], chain[7]) : make_uint4(0, 0, 0, 0);
-    pend[2] = ok ? make_uint4(hash[0], hash[1], hash[2], hash[3]) : make_uint4(0, 0, 0, 0);
-    pend[3] = ok ? make_uint4(hash[4], hash[5], hash[6], hash[7]) : make_uint4(0, 0, 0, 0);
-    pend[4] = ok ? make_uint4(esk[0], esk[1], esk[2], esk[3]) : make_uint4(0, 0, 0, 0);
-    pend[5] = ok ? make_uint4(esk[4], esk[5], esk[6], esk[7]) : make_uint4(0, 0, 0, 0);
+    uint4 *pend = a.pending + 8ull * i;
+    store_or_zero(a.messages + 10ull * i, w, 10, ok);
+    store_or_zero(pend, ns.chain, 2, ok);
+    store_or_zero(pend + 2, ns.hash, 2, ok);
+    store_or_zero(pend + 4, esk, 2, ok);
     pend[6] = ok ? make_uint4(peer, w[1], 0, 0) : make_uint4(RG_PEER_NONE, 0, 0, 0);
     pend[7] = make_uint4(0, 0, 0, 0);
     a.status[i] = (uint8_t)st; // after the rows
@@ -508,27 +372,20 @@ struct HsFinishArgs {
     uint32_t n;
 };
 
-constexpr uint32_t kRespLen = 92; // HandshakeResp (rustyguard-types)
-
+// <- e, ee, se, psk, {}, read; split(true)
 __global__ __launch_bounds__(kHsWG) void handshake_finish_kernel(HsFinishArgs a) {
     const uint32_t i = blockIdx.x * kHsWG + threadIdx.x;
     if (i >= a.n) return;
     const rg_pkt_desc d = a.desc[i];
-    uint32_t st = kGoing;
-    if ((d.offset & 15u) != 0) st = RG_PKT_UNALIGNED;
-    else if (d.offset > a.buf_len || d.len > a.buf_len - d.offset || d.len != kRespLen) st = RG_PKT_INVALID;
-    else if ((a.gate && a.gate[i] != RG_PKT_OK) || d.key_idx == RG_KEY_SKIP) st = RG_PKT_REJECTED;
+    uint32_t st = frame_verdict(d, a.gate ? a.gate[i] : (uint32_t)RG_PKT_OK, a.buf_len, kRespLen);
 
     uint32_t m[16] = {}; // the message's first 64 bytes: type, sender, receiver, ephemeral 3..11, empty 11..15
-    uint32_t chain[8] = {}, hash[8] = {}, esk[8] = {}, recv[8] = {};
+    uint32_t chain[8] = {}, hash[8] = {};
+    Noise ns{chain, hash};
+    uint32_t esk[8] = {}, recv[8] = {};
     uint32_t row = RG_PEER_NONE, peer = RG_PEER_NONE;
     if (st == kGoing) {
-        const uint4 *mp = reinterpret_cast<const uint4 *>(a.buf + d.offset);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint4 v = mp[q];
-            m[4 * q] = v.x; m[4 * q + 1] = v.y; m[4 * q + 2] = v.z; m[4 * q + 3] = v.w;
-        }
+        load_words<16>(reinterpret_cast<const uint4 *>(a.buf + d.offset), m);
         if (m[0] != 2u) st = RG_PKT_INVALID; // Error::InvalidMessage
     }
     if (st == kGoing) {
@@ -544,18 +401,14 @@ __global__ __launch_bounds__(kHsWG) void handshake_finish_kernel(HsFinishArgs a)
     }
     if (st == kGoing) {
         const uint4 *pr = a.pending + 8ull * row;
-        const uint4 r0 = pr[0], r1 = pr[1], r2 = pr[2], r3 = pr[3], r4 = pr[4], r5 = pr[5];
-        chain[0] = r0.x; chain[1] = r0.y; chain[2] = r0.z; chain[3] = r0.w;
-        chain[4] = r1.x; chain[5] = r1.y; chain[6] = r1.z; chain[7] = r1.w;
-        hash[0] = r2.x; hash[1] = r2.y; hash[2] = r2.z; hash[3] = r2.w;
-        hash[4] = r3.x; hash[5] = r3.y; hash[6] = r3.z; hash[7] = r3.w;
-        esk[0] = r4.x; esk[1] = r4.y; esk[2] = r4.z; esk[3] = r4.w;
-        esk[4] = r5.x; esk[5] = r5.y; esk[6] = r5.z; esk[7] = r5.w;
-        uint32_t sk[8], e[12] = {}, none[8], nh[8];
+        load_words<8>(pr, ns.chain);
+        load_words<8>(pr + 2, ns.hash);
+        load_words<8>(pr + 4, esk);
+        uint32_t sk[8], e[12] = {};
         load8(a.own, sk);
 #pragma unroll
         for (int q = 0; q < 8; ++q) e[q] = m[3 + q];
-        b2s_hash32(hash, e, 8, nh); // <- e: mix_hash; its mix_chain is step 0 below
+        ns.mix_hash(e, 8); // <- e; its mix_chain is step 0 below
         // every step ends in mix_chain: of the responder's ephemeral key (step 0, no ladder), of ee (step 1,
         // under our ephemeral key) and of se (step 2, under our static key)
 #pragma unroll 1
@@ -571,32 +424,26 @@ __global__ __launch_bounds__(kHsWG) void handshake_finish_kernel(HsFinishArgs a)
                 st = RG_PKT_KEYEXCHANGE;
                 continue;
             }
-            b2s_hkdf(chain, mix, 32, 0, none, none);
+            ns.mix_chain(mix);
         }
         if (st == kGoing) {
-            // <- psk: mix_key_and_hash; the empty field's tag under aad = hash
-            uint32_t psk[8], t[12] = {}, key[8], zero[8] = {}, stream[16], tag[4], diff = 0;
+            // <- psk, then the empty payload's tag
+            uint32_t psk[8], key[8], tag[4];
             load8(a.peers + 24ull * peer + 8, psk);
-            b2s_hkdf(chain, psk, 32, 2, t, key);
-            b2s_hash32(nh, t, 8, hash);
-            hs_aead(key, hash, zero, 0, stream, tag);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) diff |= tag[q] ^ m[11 + q];
-            if (diff != 0) {
+            ns.mix_key_and_hash(psk, key);
+            ns.empty_tag(key, tag);
+            if (tag_diff(tag, m + 11) != 0) {
                 st = RG_PKT_DECRYPT_ERR;
             } else {
-                // split(true): send under the new chain, receive under HKDF's second output
-                b2s_hkdf(chain, zero, 0, 1, recv, none);
+                ns.split(recv);      // split(true): send under the new chain, receive under HKDF's second output
                 st = RG_PKT_PENDING; // the commit kernel decides between the messages that got this far
             }
         }
     }
     const bool ok = st == RG_PKT_PENDING;
     uint4 *tk = a.tkeys + 4ull * i;
-    tk[0] = ok ? make_uint4(chain[0], chain[1], chain[2], chain[3]) : make_uint4(0, 0, 0, 0);
-    tk[1] = ok ? make_uint4(chain[4], chain[5], chain[6], chain[7]) : make_uint4(0, 0, 0, 0);
-    tk[2] = ok ? make_uint4(recv[0], recv[1], recv[2], recv[3]) : make_uint4(0, 0, 0, 0);
-    tk[3] = ok ? make_uint4(recv[4], recv[5], recv[6], recv[7]) : make_uint4(0, 0, 0, 0);
+    store_or_zero(tk, ns.chain, 2, ok);
+    store_or_zero(tk + 2, recv, 2, ok);
     a.pend_idx[i] = ok ? row : RG_PEER_NONE;
     a.remote[i] = ok ? m[1] : 0u;
     a.status[i] = (uint8_t)st; // after the row
@@ -630,7 +477,10 @@ __global__ __launch_bounds__(kHsWG) void handshake_commit_kernel(HsFinishArgs a)
 using namespace rg::host;
 
 namespace {
-uint32_t grid(size_t n) { return (uint32_t)((n + rg::kHsWG - 1) / rg::kHsWG); }
+const dim3 kHsBlock(rg::kHsWG);
+
+template <class T> const uint32_t *words(const T *p) { return reinterpret_cast<const uint32_t *>(p); }
+template <class T> uint4 *quads(T *p) { return reinterpret_cast<uint4 *>(p); }
 } // namespace
 
 extern "C" int rg_x25519_batch_dev(rg_ctx *ctx, const uint8_t *scalars, const uint8_t *points, uint8_t *out,
@@ -639,16 +489,16 @@ extern "C" int rg_x25519_batch_dev(rg_ctx *ctx, const uint8_t *scalars, const ui
     const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
-    if (!scalars || !out || !status || n > 0xFFFFFFFFull) return set_err(RG_EINVAL, "x25519: bad args");
+    if (!scalars || !out || !status || n > 0xFFFFFFFFull) return bad("x25519", "bad args");
     if (misaligned(scalars, 4) || misaligned(points, 4) || misaligned(out, 4))
-        return set_err(RG_EINVAL, "x25519: rows must be 4-byte aligned");
+        return bad("x25519", "rows must be 4-byte aligned");
     rg::X25519Args a{};
-    a.scalars = reinterpret_cast<const uint32_t *>(scalars);
-    a.points = reinterpret_cast<const uint32_t *>(points);
+    a.scalars = words(scalars);
+    a.points = words(points);
     a.out = reinterpret_cast<uint32_t *>(out);
     a.status = status;
     a.n = (uint32_t)n;
-    hipLaunchKernelGGL(rg::x25519_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::x25519_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "x25519 launch");
     return RG_OK;
 }
@@ -657,20 +507,20 @@ extern "C" int rg_handshake_init_batch_dev(rg_ctx *ctx, const rg_hs_static *own,
                                            uint32_t npeers, const uint32_t *peer_table, uint32_t cap,
                                            const rg_pkt_desc *desc, const uint8_t *gate, size_t n, const uint8_t *buf,
                                            size_t buf_len, rg_hs_init_result *results, uint8_t *status, void *stream) {
+    const char *const what = "handshake init";
     rg::DeviceGuard dg_;
     const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!own || !peer_table || !desc || !buf || !results || !status || (npeers && !peers) || n > 0xFFFFFFFFull)
-        return set_err(RG_EINVAL, "handshake init: bad args");
-    if (cap == 0 || (cap & (cap - 1)) != 0) return set_err(RG_EINVAL, "handshake init: cap must be a power of two");
+        return bad(what, "bad args");
+    if (!pow2(cap)) return bad(what, "cap must be a power of two");
     if (misaligned(own, 16) || misaligned(peers, 16) || misaligned(desc, 16) || misaligned(results, 16) ||
         misaligned(peer_table, 4))
-        return set_err(RG_EINVAL, "handshake init: own, peers, desc and results must be 16-byte aligned, "
-                                  "peer_table 4-byte aligned");
+        return bad(what, "own, peers, desc and results must be 16-byte aligned, peer_table 4-byte aligned");
     rg::HsInitArgs a{};
-    a.own = reinterpret_cast<const uint32_t *>(own);
-    a.peers = reinterpret_cast<const uint32_t *>(peers);
+    a.own = words(own);
+    a.peers = words(peers);
     a.npeers = npeers;
     a.table = peer_table;
     a.cap = cap;
@@ -678,10 +528,10 @@ extern "C" int rg_handshake_init_batch_dev(rg_ctx *ctx, const rg_hs_static *own,
     a.gate = gate;
     a.buf = buf;
     a.buf_len = buf_len;
-    a.results = reinterpret_cast<uint4 *>(results);
+    a.results = quads(results);
     a.status = status;
     a.n = (uint32_t)n;
-    hipLaunchKernelGGL(rg::handshake_init_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::handshake_init_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "handshake init launch");
     return RG_OK;
 }
@@ -691,31 +541,32 @@ extern "C" int rg_handshake_resp_batch_dev(rg_ctx *ctx, const rg_hs_peer *peers,
                                            const uint32_t *session_ids, const uint8_t *cookies,
                                            const uint8_t *has_cookie, size_t n, uint8_t *responses,
                                            uint8_t *transport_keys, uint8_t *status, void *stream) {
+    const char *const what = "handshake resp";
     rg::DeviceGuard dg_;
     const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!results || !esk || !session_ids || !responses || !transport_keys || !status || (npeers && !peers) ||
         (cookies && !has_cookie) || n > 0xFFFFFFFFull)
-        return set_err(RG_EINVAL, "handshake resp: bad args");
+        return bad(what, "bad args");
     if (misaligned(peers, 16) || misaligned(results, 16) || misaligned(responses, 16) || misaligned(transport_keys, 16) ||
         misaligned(esk, 4) || misaligned(session_ids, 4) || misaligned(cookies, 4))
-        return set_err(RG_EINVAL, "handshake resp: peers, results, responses and transport_keys must be 16-byte "
-                                  "aligned, esk, session_ids and cookies 4-byte aligned");
+        return bad(what, "peers, results, responses and transport_keys must be 16-byte aligned, esk, session_ids and "
+                         "cookies 4-byte aligned");
     rg::HsRespArgs a{};
-    a.peers = reinterpret_cast<const uint32_t *>(peers);
+    a.peers = words(peers);
     a.npeers = npeers;
-    a.results = reinterpret_cast<uint4 *>(results);
+    a.results = quads(results);
     a.gate = gate;
-    a.esk = reinterpret_cast<const uint32_t *>(esk);
+    a.esk = words(esk);
     a.session_ids = session_ids;
-    a.cookies = reinterpret_cast<const uint32_t *>(cookies);
+    a.cookies = words(cookies);
     a.has_cookie = has_cookie;
-    a.responses = reinterpret_cast<uint4 *>(responses);
-    a.tkeys = reinterpret_cast<uint4 *>(transport_keys);
+    a.responses = quads(responses);
+    a.tkeys = quads(transport_keys);
     a.status = status;
     a.n = (uint32_t)n;
-    hipLaunchKernelGGL(rg::handshake_resp_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::handshake_resp_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "handshake resp launch");
     return RG_OK;
 }
@@ -726,34 +577,35 @@ extern "C" int rg_handshake_initiate_batch_dev(rg_ctx *ctx, const rg_hs_static *
                                                const uint32_t *session_ids, const uint8_t *cookies,
                                                const uint8_t *has_cookie, size_t n, uint8_t *messages,
                                                rg_hs_pending *pending, uint8_t *status, void *stream) {
+    const char *const what = "handshake initiate";
     rg::DeviceGuard dg_;
     const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!own || !peer_idx || !esk || !timestamps || !session_ids || !messages || !pending || !status ||
         (npeers && !peers) || (cookies && !has_cookie) || n > 0xFFFFFFFFull)
-        return set_err(RG_EINVAL, "handshake initiate: bad args");
+        return bad(what, "bad args");
     if (misaligned(own, 16) || misaligned(peers, 16) || misaligned(messages, 16) || misaligned(pending, 16) ||
         misaligned(peer_idx, 4) || misaligned(esk, 4) || misaligned(timestamps, 4) || misaligned(session_ids, 4) ||
         misaligned(cookies, 4))
-        return set_err(RG_EINVAL, "handshake initiate: own, peers, messages and pending must be 16-byte aligned, "
-                                  "peer_idx, esk, timestamps, session_ids and cookies 4-byte aligned");
+        return bad(what, "own, peers, messages and pending must be 16-byte aligned, peer_idx, esk, timestamps, "
+                         "session_ids and cookies 4-byte aligned");
     rg::HsInitiateArgs a{};
-    a.own = reinterpret_cast<const uint32_t *>(own);
-    a.peers = reinterpret_cast<const uint32_t *>(peers);
+    a.own = words(own);
+    a.peers = words(peers);
     a.npeers = npeers;
     a.peer_idx = peer_idx;
     a.gate = gate;
-    a.esk = reinterpret_cast<const uint32_t *>(esk);
-    a.ts = reinterpret_cast<const uint32_t *>(timestamps);
+    a.esk = words(esk);
+    a.ts = words(timestamps);
     a.session_ids = session_ids;
-    a.cookies = reinterpret_cast<const uint32_t *>(cookies);
+    a.cookies = words(cookies);
     a.has_cookie = has_cookie;
-    a.messages = reinterpret_cast<uint4 *>(messages);
-    a.pending = reinterpret_cast<uint4 *>(pending);
+    a.messages = quads(messages);
+    a.pending = quads(pending);
     a.status = status;
     a.n = (uint32_t)n;
-    hipLaunchKernelGGL(rg::handshake_initiate_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(rg::handshake_initiate_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, (hipStream_t)stream, a);
     RG_HIP(hipGetLastError(), "handshake initiate launch");
     return RG_OK;
 }
@@ -764,33 +616,33 @@ extern "C" int rg_handshake_finish_batch_dev(rg_ctx *ctx, const rg_hs_static *ow
                                              const uint8_t *gate, size_t n, const uint8_t *buf, size_t buf_len,
                                              uint8_t *transport_keys, uint32_t *pend_idx_out, uint32_t *remote_out,
                                              uint32_t *claim, uint8_t *status, void *stream) {
+    const char *const what = "handshake finish";
     rg::DeviceGuard dg_;
     const int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
     if (!own || !pend_table || !pending || !desc || !buf || !transport_keys || !pend_idx_out || !remote_out ||
         !claim || !status || (npeers && !peers) || n > 0xFFFFFFFFull)
-        return set_err(RG_EINVAL, "handshake finish: bad args");
-    if (pend_cap == 0 || (pend_cap & (pend_cap - 1)) != 0)
-        return set_err(RG_EINVAL, "handshake finish: pend_cap must be a power of two");
+        return bad(what, "bad args");
+    if (!pow2(pend_cap)) return bad(what, "pend_cap must be a power of two");
     if (misaligned(own, 16) || misaligned(peers, 16) || misaligned(pending, 16) || misaligned(desc, 16) ||
         misaligned(transport_keys, 16) || misaligned(pend_table, 4) || misaligned(pend_idx_out, 4) ||
         misaligned(remote_out, 4) || misaligned(claim, 4))
-        return set_err(RG_EINVAL, "handshake finish: own, peers, pending, desc and transport_keys must be 16-byte "
-                                  "aligned, pend_table, pend_idx_out, remote_out and claim 4-byte aligned");
+        return bad(what, "own, peers, pending, desc and transport_keys must be 16-byte aligned, pend_table, "
+                         "pend_idx_out, remote_out and claim 4-byte aligned");
     rg::HsFinishArgs a{};
-    a.own = reinterpret_cast<const uint32_t *>(own);
-    a.peers = reinterpret_cast<const uint32_t *>(peers);
+    a.own = words(own);
+    a.peers = words(peers);
     a.npeers = npeers;
     a.table = pend_table;
     a.cap = pend_cap;
-    a.pending = reinterpret_cast<uint4 *>(pending);
+    a.pending = quads(pending);
     a.npending = npending;
     a.desc = desc;
     a.gate = gate;
     a.buf = buf;
     a.buf_len = buf_len;
-    a.tkeys = reinterpret_cast<uint4 *>(transport_keys);
+    a.tkeys = quads(transport_keys);
     a.pend_idx = pend_idx_out;
     a.remote = remote_out;
     a.claim = claim;
@@ -798,9 +650,9 @@ extern "C" int rg_handshake_finish_batch_dev(rg_ctx *ctx, const rg_hs_static *ow
     a.n = (uint32_t)n;
     hipStream_t s = (hipStream_t)stream;
     if (npending) RG_HIP(hipMemsetAsync(claim, 0xFF, (size_t)npending * sizeof(uint32_t), s), "handshake finish claim");
-    hipLaunchKernelGGL(rg::handshake_finish_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, s, a);
+    hipLaunchKernelGGL(rg::handshake_finish_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, s, a);
     RG_HIP(hipGetLastError(), "handshake finish launch");
-    hipLaunchKernelGGL(rg::handshake_commit_kernel, dim3(grid(n)), dim3(rg::kHsWG), 0, s, a);
+    hipLaunchKernelGGL(rg::handshake_commit_kernel, lanes(n, rg::kHsWG), kHsBlock, 0, s, a);
     RG_HIP(hipGetLastError(), "handshake finish commit launch");
     return RG_OK;
 }

@@ -362,9 +362,11 @@ int check_workspace(const char *what, const void *table, const void *workspace, 
 
 // What the entry points beside their kernels share.  p is not a multiple of a, a power of two (null is aligned):
 inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
-// one lane per item: the workgroup, and the grid of n items, computed in 64 bits
+// a table capacity the probes can mask with: a power of two, not zero
+inline bool pow2(uint64_t v) { return v != 0 && (v & (v - 1)) == 0; }
+// one lane per item: the workgroup, and the grid of n items in workgroups of wg lanes, computed in 64 bits
 inline const dim3 kWg(256);
-inline dim3 lanes(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
+inline dim3 lanes(uint64_t n, uint32_t wg = 256) { return dim3((uint32_t)((n + wg - 1) / wg)); }
 // RG_EINVAL, recorded as "what: why"
 inline int bad(const char *what, const char *why) {
     char buf[200];

@@ -32,9 +32,9 @@
 // The entry points' host side is here too (rg_cookie.hip's precedent), on rg_host.h like the host units, none
 // of which names a launcher of this file.  All scratch is the caller's; nothing is allocated, waited for or
 // kept in the context.
-#include "rg_device.h"
 #include "rg_host.h"
 #include "rg_grouped.h"
+#include "rg_noise.h"
 
 namespace rg {
 namespace {
@@ -218,19 +218,14 @@ struct ConsumeArgs {
     uint32_t n;
 };
 
-constexpr uint32_t kCookieLen = 64; // CookieMessage (rustyguard-types)
-
 // decrypt_cookie for one message per lane: the open of rg_cookie.hip's seal, out of place
 __global__ __launch_bounds__(256) void cookie_consume_kernel(ConsumeArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
     const rg_pkt_desc d = a.desc[i];
     uint32_t cookie[4] = {0, 0, 0, 0}, peer = RG_PEER_NONE;
-    uint8_t st;
-    if ((d.offset & 15u) != 0) st = RG_PKT_UNALIGNED;
-    else if (d.offset > a.buf_len || d.len > a.buf_len - d.offset || d.len != kCookieLen) st = RG_PKT_INVALID;
-    else if ((a.gate && a.gate[i] != RG_PKT_OK) || d.key_idx == RG_KEY_SKIP) st = RG_PKT_REJECTED;
-    else {
+    uint32_t st = frame_verdict(d, a.gate ? a.gate[i] : (uint32_t)RG_PKT_OK, a.buf_len, kCookieLen);
+    if (st == kGoing) {
         const uint4 *mp = reinterpret_cast<const uint4 *>(a.buf + d.offset);
         const uint4 m0 = mp[0]; // type, receiver, nonce[0..8]
         if (m0.x != 3u) st = RG_PKT_INVALID; // Error::InvalidMessage
@@ -239,32 +234,21 @@ __global__ __launch_bounds__(256) void cookie_consume_kernel(ConsumeArgs a) {
         else {
             const uint4 m1 = mp[1], ct = mp[2], tg = mp[3];
             const uint4 mac1 = a.state[(uint64_t)kStateQuads * peer + 2]; // the AAD: last_sent_mac1
-            const uint32_t hn[4] = {m0.z, m0.w, m1.x, m1.y};
-            const Key8 sub = hchacha20(load_key(a.keys, peer), hn);
-            uint32_t otk[16], stream[16];
-            chacha_block(sub, 0, 0, m1.z, m1.w, otk); // one-time Poly1305 key
-            chacha_block(sub, 1, 0, m1.z, m1.w, stream);
-            const Mul r = make_mul(otk[0], otk[1], otk[2], otk[3]);
-            Acc acc = {0, 0, 0, 0, 0};
-            acc_block(acc, mac1, r);       // AAD: 16 bytes, no padding
-            acc_block(acc, ct, r);         // ciphertext: 16 bytes
-            acc_add(acc, 16, 0, 16, 0, 1); // le64(aad_len) || le64(ct_len)
-            acc_mul(acc, r);
+            const uint32_t nonce[6] = {m0.z, m0.w, m1.x, m1.y, m1.z, m1.w}, theirs[4] = {tg.x, tg.y, tg.z, tg.w};
             uint32_t tag[4];
-            acc_finish(acc, otk[4], otk[5], otk[6], otk[7], tag);
-            const uint32_t diff = (tag[0] ^ tg.x) | (tag[1] ^ tg.y) | (tag[2] ^ tg.z) | (tag[3] ^ tg.w); // no early exit
-            const bool ok = diff == 0;
-            cookie[0] = ok ? ct.x ^ stream[0] : 0u;
-            cookie[1] = ok ? ct.y ^ stream[1] : 0u;
-            cookie[2] = ok ? ct.z ^ stream[2] : 0u;
-            cookie[3] = ok ? ct.w ^ stream[3] : 0u;
+            const uint4 pt = cookie_aead(load_key(a.keys, peer), nonce, mac1, ct, false, tag);
+            const bool ok = tag_diff(tag, theirs) == 0; // no early exit
+            cookie[0] = ok ? pt.x : 0u;
+            cookie[1] = ok ? pt.y : 0u;
+            cookie[2] = ok ? pt.z : 0u;
+            cookie[3] = ok ? pt.w : 0u;
             st = ok ? RG_PKT_OK : RG_PKT_DECRYPT_ERR;
         }
     }
     uint32_t *out = a.cookies_out + 4ull * i;
 #pragma unroll
     for (int w = 0; w < 4; ++w) out[w] = cookie[w];
-    a.status[i] = st; // after the row
+    a.status[i] = (uint8_t)st; // after the row
     if (st == RG_PKT_OK) atomicMax(&a.claim[peer], i + 1); // the maximum is the same whatever order the lanes arrive in
 }
 
@@ -394,7 +378,7 @@ extern "C" int rg_peer_cookie_consume_batch_dev(rg_ctx *ctx, rg_hs_peer_state *s
     if (!sess_table || !desc || !buf || !cookies_out || !status || (npeers && (!state || !cookie_keys || !claim)) ||
         n > 0xFFFFFFFFull)
         return set_err(RG_EINVAL, "peer cookie consume: bad args");
-    if (sess_cap == 0 || (sess_cap & (sess_cap - 1)) != 0)
+    if (!pow2(sess_cap))
         return set_err(RG_EINVAL, "peer cookie consume: sess_cap must be a power of two");
     if (misaligned(state, 16) || misaligned(cookie_keys, 16) || misaligned(desc, 16) || misaligned(sess_table, 4) ||
         misaligned(cookies_out, 4) || misaligned(claim, 4))

@@ -392,7 +392,7 @@ extern "C" int rg_recv_batch_dev_resident(rg_ctx *ctx, const uint8_t *keys, uint
     int rc = check_ctx(ctx);
     if (rc) return rc;
     if (n == 0) return RG_OK;
-    if (!keys || nkeys == 0 || !rx_table || rx_cap == 0 || (rx_cap & (rx_cap - 1)) != 0 || !windows || !desc || !buf ||
+    if (!keys || nkeys == 0 || !rx_table || !pow2(rx_cap) || !windows || !desc || !buf ||
         !status || !workspace || n > 0xFFFFFFFFull)
         return set_err(RG_EINVAL, "recv resident: bad args");
     const rg::ReplayLayout L = rg::replay_layout(n, nkeys);
