@@ -350,8 +350,9 @@ int rg_handshake_resp_batch_dev(rg_ctx *ctx, const rg_hs_peer *peers, uint32_t n
  * and be captured into a graph); n == 0 returns RG_OK; RG_EINVAL with nothing enqueued for a null required
  * pointer, n > 2^32 - 1 or a misaligned array.  Struct rows, desc, messages and transport_keys must be 16-byte
  * aligned, word arrays (peer_idx, esk, timestamps, session_ids, cookies, pend_table, pend_idx_out, remote_out,
- * claim) 4-byte aligned.  Choosing session ids, timers, the peer's endpoint and current_handshake stay with the
- * caller; installing the finished sessions is rg_session_install_finish_batch_dev's (further down).
+ * claim) 4-byte aligned.  Choosing session ids and the peer's endpoint stay with the caller; current_handshake and
+ * the retry and expiry timers are the pending-handshake section's, and installing the finished sessions is
+ * rg_session_install_finish_batch_dev's (both further down).
  *
  * Randomness and time: the library has no RNG and no clock.  esk[i] must be 32 fresh bytes of the caller's
  * CSPRNG for every row of every call (EphemeralPrivateKey::generate, handshake.rs:275), never reused;
@@ -1101,8 +1102,8 @@ int rg_session_index_dev(rg_ctx *ctx, const rg_session_tables *tables, void *str
 /* What Sessions::turn (rustyguard-core/src/time.rs:42-140, tick_timers) decides for transport sessions, on the
  * stream that sends and receives: which sessions owe a keepalive and which peers owe a new handshake, as the
  * arrays rg_send_batch_dev_resident and the initiator chain take.  Expiry stays rg_session_expire_batch_dev, run
- * behind the turn.  The handshake-side timers (InitAttempt, ExpireHandshake, current_handshake) stay with the
- * caller.
+ * behind the turn.  The handshake-side timers (InitAttempt, ExpireHandshake, current_handshake) are the next
+ * section's, whose turn takes this turn's rekey list.
  *
  * The conventions are the session-table section's: every array is device memory; the calls enqueue on `stream`
  * and return without waiting, allocate nothing and keep nothing in the context (so they can be captured into a
@@ -1188,6 +1189,126 @@ int rg_timer_turn_dev(rg_ctx *ctx, const rg_session_tables *tables, rg_session_t
                       uint32_t *ka_slots_out /* [npeers] */, uint32_t *rekey_peers_out /* [npeers] */,
                       uint8_t *rekey_gate_out /* [npeers] */, uint32_t counts_out[2], void *workspace,
                       size_t workspace_len, void *stream);
+
+/* ------------------------------ device-resident pending handshakes (batch, async) */
+/* The initiator's side of Sessions between "this peer needs a handshake" and "its response arrived", on the
+ * stream that sends and receives: the pending-handshake table with Peer.current_handshake, and the two
+ * handshake-side timers, InitAttempt and ExpireHandshake (rustyguard-core/src/time.rs:49-83, 99-113; armed in
+ * handshake.rs:260-325).  Three calls on a running tunnel name peers that need a handshake -- rg_timer_turn_dev's
+ * rekey list, the routed send's RG_PKT_REJECTED rows with their peers_out, and an initiation that got no answer
+ * for REKEY_TIMEOUT -- and rg_pending_turn_dev merges all three into the one list the initiator chain takes;
+ * rg_pending_install_batch_dev puts the chain's pending rows into the table rg_handshake_finish_batch_dev reads.
+ * No host read lies between a lost packet and its retry.
+ *
+ * The conventions are the session-table and timer sections': every array is device memory; the calls enqueue on
+ * `stream` and return without waiting, allocate nothing and keep nothing in the context (so they can be captured
+ * into a graph; every fill is a kernel, no memset node); now_ns points at one uint64_t in device memory, read when
+ * the kernels run; n == 0 returns RG_OK; RG_EINVAL with nothing enqueued -- and before the device is touched at
+ * all -- for a null required pointer (gate, expired_out and start_status are optional, start_peers when m == 0, the
+ * three per-peer table arrays when npeers == 0), a count above 2^32 - 1, a misaligned array (struct rows 16 bytes;
+ * rg_pending_timer rows, pend_table and now_ns 8; word arrays 4; the workspace 16), pend_cap not a power of two
+ * or < 2 npeers, or a workspace smaller than rg_pending_workspace_size(n, m, npeers) reports (0 when a size is
+ * above 2^32 - 1; non-decreasing in each argument; the install is asked with m = 0, the turn with n = 0).  The
+ * workspace belongs to one call at a time.  A lane stores its status after everything else it writes.  All time
+ * arithmetic is the u64 wrapping add and strict < of rg_send_reserve_batch_dev.  Nothing is decided by the order
+ * the lanes arrive in.
+ *
+ * The table is indexed by peer: current_handshake holds at most one pending handshake a peer.  The caller owns
+ * the arrays and passes them in a host struct that is read at call time.  An empty table has `pending` zeroed with
+ * peer = RG_PEER_NONE, pend_table 0xFF and the rest zero.  Liveness has one source, pending[p].peer == p: the
+ * finish call's wipe of a row ends its life with no further call, and a stale pend_table entry that names a
+ * wiped row is harmless (the finish call answers RG_PKT_REJECTED).  rg_handshake_finish_batch_dev is used with
+ * pending = tables.pending and npending = npeers, so its pend_idx_out is the peer;
+ * rg_session_install_finish_batch_dev with pend_session_ids = hs_ids and pend_peers = the caller's constant array
+ * 0..npeers-1. */
+#define RG_REKEY_TIMEOUT_NS       5000000000ull   /* REKEY_TIMEOUT, lib.rs:69 */
+#define RG_REKEY_ATTEMPT_TIME_NS 90000000000ull   /* REKEY_ATTEMPT_TIME, lib.rs:68 */
+typedef struct rg_pending_timer {    /* 16 bytes, 8-byte aligned: Session.started / .sent of a handshake */
+    uint64_t started_ns;             /* the first attempt of this run of retries */
+    uint64_t sent_ns;                /* the latest attempt */
+} rg_pending_timer;
+typedef struct rg_pending_tables {
+    rg_hs_pending    *pending;    /* [npeers]   row p is peer p's current_handshake; live iff pending[p].peer == p */
+    rg_pending_timer *timers;     /* [npeers]   meaningful for live rows only                                     */
+    uint32_t         *hs_ids;     /* [npeers]   sender id of the last handshake installed for p; survives the     */
+                                  /*            finish call's wipe                                                */
+    rg_rx_entry      *pend_table; /* [pend_cap] receiver id -> p over the live rows; pend_cap a power of two      */
+                                  /*            >= 2 npeers                                                       */
+    uint32_t npeers, pend_cap;
+} rg_pending_tables;
+
+/* rg_pending_index_dev rebuilds pend_table from the live rows: a fill with 0xFF, then one lane per live row claims
+ * the first empty entry from its id's home slot (the receiver-table rebuild's method).  Probing is bounded by
+ * pend_cap, and no index leaves the table.
+ *
+ * rg_pending_install_batch_dev is the tail of new_handshake (handshake.rs:266-297), run behind
+ * rg_handshake_initiate_batch_dev on its pending[n] output (`batch`) and its status (`gate`).  Its result equals
+ * this loop, bit for bit on status, installed_out, every byte of batch, tables.pending, timers and hs_ids, and on
+ * pend_table through its lookup:
+ *   now = *now_ns;  live0[p] = (pending[p].peer == p) before the call
+ *   for i in array order:
+ *     installed_out[i] = RG_PEER_NONE
+ *     gate && gate[i] != RG_PKT_OK -> status RG_PKT_REJECTED; nothing else of row i read or written
+ *     row = batch[i]; batch[i] = zeros with peer = RG_PEER_NONE    (a pending row is consumed once, whatever follows)
+ *     p = row.peer;  p >= npeers -> RG_PKT_INVALID
+ *     status RG_PKT_OK
+ *     the LAST such i of a peer p in array order is stored:        (each new_handshake replaces the one before)
+ *       pending[p] = row; hs_ids[p] = row.sender
+ *       timers[p] = { live0[p] ? timers[p].started_ns : now, now } (handshake.rs:281-293: a retry keeps `started`)
+ *       installed_out[i] = p
+ *   pend_table = the table over the live rows
+ * computed with atomicMax(claim[p], i + 1), a commit over the peers that moves the 128-byte row in 16-byte pieces,
+ * and a wipe over the batch that runs after the commit has read it.  batch must not overlap tables.pending
+ * (RG_EINVAL).  Sender ids are the caller's and must be unique among live rows; with a repeat the call stays
+ * memory-safe, and which row the lookup answers is unspecified.
+ *
+ * rg_pending_turn_dev is the InitAttempt and ExpireHandshake arms of tick_timers for the whole table, and the
+ * merge of every other source of "this peer needs a handshake" into one list, so that a turn costs one initiate
+ * call whatever the number of sources.  start_peers[m] / start_status[m] / start_match is a request list: entry j
+ * counts iff start_status == NULL or start_status[j] == start_match.  That fits rg_timer_turn_dev's
+ * rekey_peers_out / rekey_gate_out with RG_PKT_OK and the routed send's peers_out / status with RG_PKT_REJECTED;
+ * the call is made once per source, or once on a concatenation the caller keeps.  Its result equals this loop, bit
+ * for bit on every byte of tables.pending and timers, on the three output arrays over their full npeers and on
+ * counts_out:
+ *   now = *now_ns; want[p] = 0; nexp = 0
+ *   for p in 0..npeers with pending[p].peer == p:
+ *     timers[p].sent_ns + 90e9 < now     -> pending[p] = zeros, peer = RG_PEER_NONE; timers[p] = 0;
+ *                                           expired_out[p] = 1; nexp++       (time.rs:99-113; armed at the attempt's
+ *                                                                             now + REKEY_ATTEMPT_TIME, handshake.rs:319-322)
+ *     else sent_ns + 5e9 < now and now < started_ns + 90e9
+ *                                        -> want[p] = 1; timers[p].sent_ns = now  (should_reinit, lib.rs:194-196;
+ *                                                                                  new_handshake stamps `sent` before it can fail)
+ *   expired_out[p] = 0 for every other p (expired_out may be NULL)
+ *   for j in 0..m that counts, q = start_peers[j] < npeers:
+ *     pending[q].peer != q (after the loop above) -> want[q] = 1
+ *   for p ascending with want[p]: init_peers_out[k++] = p
+ *   init_peers_out[k..npeers) = RG_PEER_NONE; init_gate_out = RG_PKT_OK below k, RG_PKT_REJECTED above
+ *   counts_out = {k, nexp};  pend_table = the table over the live rows (rebuilt on every call)
+ * computed with a clear kernel, one lane per peer, one lane per request and an exclusive count over the peers, both
+ * counts in one 64-bit sum.  hs_ids is written by the install only.  The two row rules cannot both hold without
+ * clock wrap: started_ns <= sent_ns, so sent_ns + 90e9 < now implies started_ns + 90e9 < now, and the second rule
+ * asks for the opposite; with a clock that wraps between them the expiry is taken, as the order above says.
+ * init_peers_out / init_gate_out are the peer_idx / gate of rg_peer_cookies_batch_dev ->
+ * rg_handshake_initiate_batch_dev -> rg_peer_mac1_batch_dev -> rg_pending_install_batch_dev, each run with the
+ * host-side n = npeers.
+ *
+ * Unlike the reference: (a) it starts a new handshake for every sessionless packet and every fired rekey, replacing
+ * one in flight (lib.rs:575-580); here a request for a peer with a live pending row is dropped and the row's own
+ * 5 s retry governs -- otherwise a batch of packets a millisecond later would replace the handshake before its
+ * response can arrive.  (b) The timers are evaluated statelessly on {started_ns, sent_ns}, not popped from a heap;
+ * the same entries fire: InitAttempt at sent + 5 s, ExpireHandshake at sent + 90 s, and no retry once
+ * now >= started + 90 s.  (c) Session ids, esk, timestamps and endpoints stay the caller's. */
+size_t rg_pending_workspace_size(size_t n, size_t m, uint32_t npeers);
+int rg_pending_index_dev(rg_ctx *ctx, const rg_pending_tables *tables, void *stream);
+int rg_pending_install_batch_dev(rg_ctx *ctx, const rg_pending_tables *tables, rg_hs_pending *batch /* [n] */,
+                                 const uint8_t *gate /* [n] or NULL */, size_t n, const uint64_t *now_ns,
+                                 uint8_t *status /* [n] */, uint32_t *installed_out /* [n] */, void *workspace,
+                                 size_t workspace_len, void *stream);
+int rg_pending_turn_dev(rg_ctx *ctx, const rg_pending_tables *tables, const uint64_t *now_ns,
+                        const uint32_t *start_peers /* [m] or NULL */, const uint8_t *start_status /* [m] or NULL */,
+                        uint8_t start_match, size_t m, uint32_t *init_peers_out /* [npeers] */,
+                        uint8_t *init_gate_out /* [npeers] */, uint8_t *expired_out /* [npeers] or NULL */,
+                        uint32_t counts_out[2], void *workspace, size_t workspace_len, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

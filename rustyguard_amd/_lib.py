@@ -145,6 +145,11 @@ SIGNATURES = {
     "rg_timer_note_send_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
     "rg_timer_note_recv_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp, c_vp]),
     "rg_timer_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_pending_workspace_size": (c_size, [c_size, c_size, c_u32]),
+    "rg_pending_index_dev": (c_int, [c_vp, c_vp, c_vp]),
+    "rg_pending_install_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "rg_pending_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint8, c_size, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_size, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

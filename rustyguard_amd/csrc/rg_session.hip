@@ -33,11 +33,12 @@
 // in the context.
 #include "rg_host.h"
 #include "rg_grouped.h"
+#include "rg_rxclaim.h"
 
 namespace rg {
 namespace {
 
-constexpr uint64_t kEmpty64 = ~0ull; // a free entry of the id table and of the receiver table
+constexpr uint64_t kEmpty64 = ~0ull; // a free entry of the id table
 constexpr uint32_t kWindowWords = sizeof(rg_antireplay) / 8;
 constexpr uint64_t kRejectAfterNs = RG_REJECT_AFTER_TIME_NS;
 
@@ -278,11 +279,7 @@ __global__ __launch_bounds__(256) void peer_commit_kernel(InstallArgs a) {
 __global__ __launch_bounds__(256) void index_kernel(Tables t) {
     const uint32_t r = blockIdx.x * 256 + threadIdx.x;
     if (r >= t.nkeys || t.slot_peer[r] == RG_PEER_NONE) return;
-    const uint32_t id = t.local_ids[r];
-    const unsigned long long mine = (unsigned long long)id | ((unsigned long long)r << 32);
-    uint32_t s = rx_slot(id, t.rx_cap) & (t.rx_cap - 1);
-    for (uint32_t probe = 0; probe < t.rx_cap; ++probe, s = (s + 1) & (t.rx_cap - 1))
-        if (atomicCAS(&t.rx_table[s], kEmpty64, mine) == kEmpty64) return;
+    rx_claim(t.rx_table, t.rx_cap, t.local_ids[r], r);
 }
 
 // ------------------------------------------------------------------ expiry

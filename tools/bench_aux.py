@@ -57,6 +57,12 @@
          and rg_timer_arm_batch_dev, rg_timer_note_send_batch_dev and rg_timer_note_recv_batch_dev at 64 Ki
          packets.  Medians of seven with min-max, by stream events.  Also written to profiles/timers_bench.json
 
+  pending  the device-resident pending handshakes at 16 Ki and 256 Ki peers with about 1 % and about 50 % of the
+         rows due for a retry: rg_pending_turn_dev (alone and fed the timer turn's rekey list),
+         rg_pending_install_batch_dev behind the chain and rg_pending_index_dev, beside rg_timer_turn_dev and the
+         bare initiator chain (cookies -> initiate -> mac1, n = npeers) in the same run.  Medians of seven with
+         min-max, by stream events.  Also written to profiles/pending_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -1155,15 +1161,134 @@ def timers_leg(eng):
     return out
 
 
+def pending_leg(eng):
+    """The device-resident pending handshakes by stream events, medians of seven with min-max, all in one run, at
+    16 Ki and 256 Ki peers with about 1 % and about 50 % of the rows due for a retry.  Every row of the pending table
+    is live; a due row was last sent REKEY_TIMEOUT and 9 ns ago.  Beside rg_pending_turn_dev, the install of the
+    chain's rows (n = npeers, the turn's gate) and the table rebuild alone: rg_timer_turn_dev over a transport table
+    of four rows per peer with the same share due, and the bare initiator chain (cookies -> initiate -> mac1,
+    n = npeers) over the turn's list.  Tables and batch are put back from saved copies between repetitions, outside
+    the timed region.  Written to profiles/pending_bench.json."""
+    from rustyguard_amd import pending, session, timers
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(73)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    words = lambda a: dev(np.asarray(a, np.uint32).view(np.int32))  # noqa: E731
+    z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")  # noqa: E731
+    now = 10**12
+    d_now = dev(np.array([now], np.int64))
+    sk_a = rng.integers(0, 256, 32, dtype=np.uint8).tobytes()
+    a_own = dev(np.frombuffer(sk_a + bytes(32), np.uint8))  # the initiate reads the private half and its own public key
+
+    def measure(fn, reset):
+        ev = []
+        for _ in range(8):  # the first is the warm-up
+            reset()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ev.append(a.elapsed_time(b))
+        ts = sorted(ev[1:])
+        return {"ms_median": round(ts[len(ts) // 2], 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4)}
+
+    out = {}
+    for npeers in (1 << 14, 1 << 18):
+        nkeys = 4 * npeers
+        P = pending.PendingTables(eng, npeers)
+        rows = rng.integers(0, 256, (npeers, 128), dtype=np.uint8)
+        rows.view(np.uint32).reshape(npeers, 32)[:, pending.PEER_WORD] = np.arange(npeers)
+        rows.view(np.uint32).reshape(npeers, 32)[:, pending.SENDER_WORD] = np.arange(npeers) + 0x4000_0000
+        saved_rows = dev(rows)
+        a_peers, state = dev(rng.integers(0, 256, (npeers, 96), dtype=np.uint8)), z(npeers, 64)
+        init, gate, expired, counts = z(npeers, dtype=torch.int32), z(npeers), z(npeers), z(2, dtype=torch.int32)
+        ws = pending.pending_workspace(eng, npeers, npeers, npeers)
+        esk, sids = dev(rng.integers(0, 256, (npeers, 32), dtype=np.uint8)), words(np.arange(npeers) + 0x5000_0000)
+        tss = dev(np.tile(np.frombuffer(bytes(12), np.uint8), (npeers, 1)))
+        cookies, has, claim = z(npeers, 16), z(npeers), z(npeers, dtype=torch.int32)
+        msgs, batch, st_i, st_p = z(npeers, 160), z(npeers, 128), z(npeers), z(npeers)
+        installed = z(npeers, dtype=torch.int32)
+        # the transport table beside it: the timers leg's, four rows per peer
+        T, tm = session.SessionTables(eng, nkeys, npeers), timers.timer_rows(eng, nkeys)
+        r = np.arange(nkeys)
+        T.slot_peer[:] = words(r % npeers)
+        T.peer_slot[:] = words(np.arange(npeers) + nkeys - npeers)
+        ka, rk, rk_gate, rk_counts = z(npeers, dtype=torch.int32), z(npeers, dtype=torch.int32), z(npeers), z(2, dtype=torch.int32)
+        ws_t = timers.timer_workspace(eng, nkeys, npeers)
+        row = {"nkeys_of_the_timer_turn": nkeys}
+        for label, share in (("1_percent", 0.01), ("50_percent", 0.5)):
+            due = rng.random(npeers) < share
+            tmr = np.zeros((npeers, 2), np.uint64)
+            tmr[:, 0] = tmr[:, 1] = np.where(due, now - 5 * 10**9 - 9, now - 1)
+            saved_tm = dev(tmr.view(np.uint8).reshape(npeers, 16))
+            due_k = rng.random(nkeys) < share
+            state_k = np.zeros((nkeys, 3), np.uint64)
+            state_k[:, 0] = 3
+            state_k[:, 1] = np.where(due_k, now - 120 * 10**9 - 9, now - 9)
+            state_k[:, 2] = np.where(due_k, now - 10 * 10**9 - 9, now - 9)
+            tm_k = np.zeros((nkeys, 2), np.uint64)
+            tm_k[:, 0] = np.where(due_k, now - 1, now + 120 * 10**9)
+            tm_k[:, 1] = due_k
+            saved_state_k, saved_tm_k = dev(state_k.view(np.uint8).reshape(nkeys, 24)), dev(tm_k.view(np.uint8).reshape(nkeys, 16))
+            saved_batch = batch.clone()
+
+            def reset():
+                P.pending.copy_(saved_rows)
+                P.timers.copy_(saved_tm)
+                batch.copy_(saved_batch)
+                T.send_state.copy_(saved_state_k)
+                tm.copy_(saved_tm_k)
+
+            turn = lambda: pending.turn_dev(eng, P, d_now, init, gate, counts, expired_out=expired, workspace=ws)  # noqa: E731
+            res = {"pending_turn": measure(turn, reset)}
+            k, nexp = (int(x) for x in counts.cpu().numpy().view(np.uint32))
+            assert k == int(due.sum()) and nexp == 0, (k, nexp, int(due.sum()))
+            res["rows_due"] = k
+            # the same turn fed the timer turn's rekey list as requests: every row is live, so none is added
+            res["timer_turn"] = measure(lambda: timers.turn_dev(eng, T, tm, d_now, ka, rk, rk_gate, rk_counts, workspace=ws_t),
+                                        reset)
+            res["rekeys_listed"] = int(rk_counts.cpu().numpy().view(np.uint32)[1])
+            res["pending_turn_with_requests"] = measure(
+                lambda: pending.turn_dev(eng, P, d_now, init, gate, counts, start_peers=rk, start_status=rk_gate,
+                                         start_match=aead.PKT_OK, expired_out=expired, workspace=ws), reset)
+            assert int(counts.cpu().numpy().view(np.uint32)[0]) == k
+            chain = lambda: (eng.peer_cookies_dev(state, init, cookies, has),  # noqa: E731
+                             eng.handshake_initiate_dev(a_own, a_peers, init, gate, esk, tss, sids, cookies, has, msgs,
+                                                        batch, st_i),
+                             eng.peer_mac1_dev(state, init, st_i, msgs, 160, 116, claim))
+            res["initiator_chain"] = measure(chain, lambda: None)
+            assert int((st_i == aead.PKT_OK).sum()) == k
+            saved_batch = batch.clone()  # the chain's rows: what the install consumes
+            res["pending_install"] = measure(
+                lambda: pending.install_dev(eng, P, batch, st_i, d_now, st_p, installed, workspace=ws), reset)
+            assert int((st_p == aead.PKT_OK).sum()) == k and int((installed != -1).sum()) == k
+            res["pending_index"] = measure(lambda: pending.index_dev(eng, P), reset)
+            row[label] = res
+        out[f"peers_{npeers}"] = row
+    out["note"] = ("stream events around one call each, medians of 7 repetitions after one warm-up; every pending row "
+                   "live, a due row last sent 5 s + 9 ns ago; pending_turn = clear + row + count + carry + rank + index "
+                   "kernels (with requests: + the request kernel, m = npeers); pending_install = clear + claim + commit "
+                   "+ wipe + index kernels, n = npeers behind the chain's statuses; pending_index = fill + index; "
+                   "timer_turn over four transport rows per peer with the same share due; initiator_chain = cookies -> "
+                   "initiate -> mac1 with n = npeers over the pending turn's list and gate")
+    with open(os.path.join(root, "profiles", "pending_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate", "session", "timers"]
+                            "peerstate", "session", "timers", "pending"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
                       ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg),
-                      ("timers", timers_leg)):
+                      ("timers", timers_leg), ("pending", pending_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
