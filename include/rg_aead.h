@@ -1310,6 +1310,92 @@ int rg_pending_turn_dev(rg_ctx *ctx, const rg_pending_tables *tables, const uint
                         uint8_t *init_gate_out /* [npeers] */, uint8_t *expired_out /* [npeers] or NULL */,
                         uint32_t counts_out[2], void *workspace, size_t workspace_len, void *stream);
 
+/* ------------------------------ device-resident handshake rate limiter (batch, async) */
+/* DynamicState::overloaded (rustyguard-core/src/lib.rs:508-514) on the stream that runs the responder chain: the
+ * count-min sketch over source addresses (rustyguard-utils/src/rate_limiter.rs, CountMinSketch::with_params(10.0 /
+ * 20_000.0, 0.01, rng)) that handle_handshake_init and handle_handshake_resp bump once per handshake message before
+ * the MACs are looked at (handshake.rs:47, :151), and Sessions::turn's wipe and reseed (lib.rs:406-408).
+ * rg_rate_count_batch_dev's overload_out is the `overload` argument of rg_cookie_reply_batch_dev on the same
+ * stream, so the filter's last input needs no host step: rg_rate_turn_dev -> rg_rate_count_batch_dev ->
+ * rg_cookie_reply_batch_dev -> the responder chain.
+ *
+ * The conventions are the session-table, timer and pending sections': every array is device memory unless marked
+ * host; the calls enqueue on `stream` and return without waiting, allocate nothing and keep nothing in the context
+ * (so they can be captured into a graph; every fill is a kernel, no memset node); now_ns points at one uint64_t in
+ * device memory, read when the kernels run; n == 0 returns RG_OK; RG_EINVAL with nothing enqueued -- and before the
+ * device is touched at all -- for a null required pointer (counts_out is optional), a count above 2^32 - 1 (n,
+ * n * depth, and width * depth, the number of buckets), a misaligned array (seeds, new_seeds and the workspace 16
+ * bytes; rg_src_addr rows, now_ns and last_reset_ns 8; word arrays 4), depth == 0, depth > RG_RATE_MAX_DEPTH,
+ * width == 0, or a workspace smaller than rg_rate_workspace_size(n, width, depth) reports (0 when a size is out of
+ * range; non-decreasing in each argument within it).  The workspace belongs to one call at a time.  Nothing is
+ * decided by the order the lanes arrive in: no atomic's return value is used.
+ *
+ * The caller owns the arrays and passes them in a host struct that is read at call time.  An empty sketch is all
+ * zero.  width and depth are free (a test can force collisions with a tiny sketch); the defaults are the
+ * reference's.
+ *
+ * Key of a source address (lib.rs:509-512): an address whose ip[4..16] is all zero is IPv4 and key = the big-endian
+ * u32 of ip[0..4]; any other address is keyed by its /64, key = the big-endian u64 of ip[0..8].  The port is
+ * ignored.
+ * Column of key in sketch row r:
+ *   fold(x, y) = the low 64 bits XOR the high 64 bits of the 128-bit product x * y
+ *   h   = fold(fold(key ^ seeds[r].a, 0x9E3779B97F4A7C15) ^ seeds[r].b, 0xD6E8FEB86659FD93)
+ *   col = (uint32_t)(((h >> 32) * width) >> 32)
+ * rg_rate_column is that column for one address and one seed, computed on the host from the code the kernels
+ * compile (NULL seed or addr: 0).
+ *
+ * rg_rate_count_batch_dev takes the desc and buf of rg_cookie_reply_batch_dev and never writes buf.  A message is
+ * counted exactly when the filter would go on to read its MACs: offset % 16 == 0, the frame inside [buf, buf +
+ * buf_len), len == 148 with type word 1 or len == 92 with type word 2, and key_idx != RG_KEY_SKIP.  Its result
+ * equals this loop, bit for bit on counts_out (may be NULL), overload_out and every bucket:
+ *   for i in array order:
+ *     not counted -> counts_out[i] = 0; overload_out[i] = 0
+ *     else est = 0xFFFFFFFF
+ *          for r in 0..depth: c = col_r(key(addrs[i])); b = buckets[r][c] = sat_add_u32(buckets[r][c], 1)
+ *                             est = min(est, b)
+ *          counts_out[i] = est; overload_out[i] = est > limit
+ * computed over the n * depth items (message, sketch row): one stable grouping by the bucket r * width + col (two
+ * 8-bit radix passes at the default size), a segmented inclusive count of the counted items, estimate =
+ * sat_add(bucket, rank); the last item of each bucket's group stores the bucket, and one lane per message takes the
+ * minimum over its depth items and stores overload_out last.
+ *
+ * rg_rate_turn_dev:
+ *   now = *now_ns; last = *last_reset_ns
+ *   now > last and now - last > period_ns -> buckets = 0; seeds = new_seeds; *last_reset_ns = now; *reset_out = 1
+ *   else                                  -> *reset_out = 0; nothing else written
+ * One lane decides and writes reset_out and last_reset_ns; the wipe behind it reads reset_out alone, so a replayed
+ * graph reads its clock when it runs.  Randomness: the library has no RNG.  new_seeds is depth fresh 16-byte
+ * outputs of the caller's CSPRNG, refreshed every turn like the cookie nonces and consumed only on a reset.
+ *
+ * Unlike the reference: (a) the hash.  The reference hashes with foldhash under random seeds that are redrawn every
+ * second; no output of that hash is observable or reproducible, and its source is not available to this project.
+ * What is kept is the contract: a keyed 64-bit hash per sketch row, seeded from the caller's RNG.  (b) The reference
+ * never assigns last_rate_reset (lib.rs:361, 376 and 406 are its only uses), so it wipes on every turn in which the
+ * clock advanced; period_ns = 0 reproduces exactly that, and RG_RATE_PERIOD_NS gives the one-second window the
+ * comparison was written for. */
+#define RG_RATE_WIDTH      5437u           /* ceil(e / (10/20000)), rate_limiter.rs:54-60 with lib.rs:377 */
+#define RG_RATE_DEPTH      5u              /* ceil(ln(1/0.01)) */
+#define RG_RATE_LIMIT      10u             /* overloaded: count > 10, lib.rs:513 */
+#define RG_RATE_MAX_DEPTH  8u
+#define RG_RATE_PERIOD_NS  1000000000ull   /* lib.rs:406 */
+typedef struct rg_rate_seed { uint64_t a, b; } rg_rate_seed;   /* 16 bytes; the caller's CSPRNG output */
+typedef struct rg_rate_tables {            /* host struct, read at call time */
+    uint32_t     *buckets;        /* [depth][width], row-major; an empty sketch is all zero */
+    rg_rate_seed *seeds;          /* [depth] */
+    uint64_t     *last_reset_ns;  /* [1], starts 0 */
+    uint32_t width, depth;
+} rg_rate_tables;
+
+uint32_t rg_rate_column(const rg_rate_seed *seed /* host */, const rg_src_addr *addr /* host */, uint32_t width);
+size_t rg_rate_workspace_size(size_t n, uint32_t width, uint32_t depth);
+int rg_rate_count_batch_dev(rg_ctx *ctx, const rg_rate_tables *tables, const rg_pkt_desc *desc,
+                            const rg_src_addr *addrs, size_t n, const uint8_t *buf, size_t buf_len, uint32_t limit,
+                            uint32_t *counts_out /* [n] or NULL */, uint8_t *overload_out /* [n] */,
+                            void *workspace, size_t workspace_len, void *stream);
+int rg_rate_turn_dev(rg_ctx *ctx, const rg_rate_tables *tables, const uint64_t *now_ns, uint64_t period_ns,
+                     const rg_rate_seed *new_seeds /* [depth], caller's CSPRNG */, uint32_t *reset_out /* [1] */,
+                     void *stream);
+
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:
  * 349-352; send_message / recv_message :542-583, :605-681).  A group lets that one thread drive

@@ -150,6 +150,11 @@ SIGNATURES = {
     "rg_pending_install_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "rg_pending_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint8, c_size, c_vp, c_vp, c_vp, c_vp, c_vp,
                                     c_size, c_vp]),
+    "rg_rate_column": (c_u32, [c_vp, c_vp, c_u32]),
+    "rg_rate_workspace_size": (c_size, [c_size, c_u32, c_u32]),
+    "rg_rate_count_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_size, c_u32, c_vp, c_vp, c_vp, c_size,
+                                        c_vp]),
+    "rg_rate_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

@@ -29,11 +29,11 @@ LIB = os.path.join(LIBDIR, "librg_aead.so")
 TEST_LIB = os.path.join(LIBDIR, "librg_aead_test.so")
 KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip",
            "rg_replay.hip", "rg_send.hip", "rg_handshake.hip", "rg_route.hip", "rg_peerstate.hip",
-           "rg_session.hip", "rg_timers.hip", "rg_pending.hip"]
+           "rg_session.hip", "rg_timers.hip", "rg_pending.hip", "rg_ratelimit.hip"]
 HOST = ["rg_ctx.cpp", "rg_batch.cpp", "rg_hostpipe.cpp", "rg_message.cpp", "rg_sessions.cpp", "rg_debug.cpp"]
 SOURCES = KERNELS + HOST
 HEADERS = ["rg_device.h", "rg_internal.h", "rg_host.h", "rg_blake2s.h", "rg_grouped.h", "rg_x25519.h",
-           "rg_route.h", "rg_noise.h", "rg_rxclaim.h"]
+           "rg_route.h", "rg_noise.h", "rg_rxclaim.h", "rg_ratehash.h"]
 ARCH = os.environ.get("RG_OFFLOAD_ARCH", "gfx950")
 # Per-file code generation.  The pipelined and flattened kernels run one wave per SIMD, so nothing hides a
 # hazard wait state: LLVM's iterative-ILP machine scheduler fills most of the s_nops the default strategy

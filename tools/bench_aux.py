@@ -63,6 +63,11 @@
          bare initiator chain (cookies -> initiate -> mac1, n = npeers) in the same run.  Medians of seven with
          min-max, by stream events.  Also written to profiles/pending_bench.json
 
+  ratelimit  the device-resident handshake rate limiter on the default sketch: rg_rate_count_batch_dev at 1 Ki and
+         64 Ki initiations from 1, 256 and 20 000 distinct source addresses, rg_cookie_reply_batch_dev on the same
+         batch beside it (fed the count's flags, and all overloaded), and rg_rate_turn_dev with and without a
+         reset.  Medians of seven with min-max, by stream events.  Also written to profiles/ratelimit_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -1280,15 +1285,119 @@ def pending_leg(eng):
     return out
 
 
+def ratelimit_leg(eng):
+    """The device-resident handshake rate limiter by stream events, medians of seven with min-max, all in one run, on
+    the default sketch (5437 x 5): rg_rate_count_batch_dev at 1 Ki and 64 Ki valid initiations from 1, 256 and 20 000
+    distinct source addresses (dealt round-robin), from an empty sketch each time; rg_cookie_reply_batch_dev on the
+    same batch beside it, fed the count's flags and all overloaded; the count of the same 320 Ki items with two, one
+    and no radix pass (where its time goes); and rg_rate_turn_dev with and without a reset.  The sketch is put back between repetitions, outside the timed region.  Written to
+    profiles/ratelimit_bench.json."""
+    from rustyguard_amd import ratelimit
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(97)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    z = lambda *shape, dtype=torch.uint8: torch.zeros(shape, dtype=dtype, device="cuda")  # noqa: E731
+    L = 148
+
+    def measure(fn, reset):
+        ev = []
+        for _ in range(8):  # the first is the warm-up
+            reset()
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ev.append(a.elapsed_time(b))
+        ts = sorted(ev[1:])
+        return {"ms_median": round(ts[len(ts) // 2], 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4)}
+
+    T = ratelimit.RateTables(eng)
+    seeds = dev(rng.integers(0, 256, (T.depth, 16), dtype=np.uint8))
+    new_seeds = dev(rng.integers(0, 256, (T.depth, 16), dtype=np.uint8))
+    ck = rng.integers(0, 256, 96, dtype=np.uint8)
+    keys, mac1_key = dev(ck), ck[:32].tobytes()
+
+    def empty():
+        T.buckets.zero_()
+        T.seeds.copy_(seeds)
+
+    out = {"width": T.width, "depth": T.depth, "limit": ratelimit.RATE_LIMIT}
+    for n in (1 << 10, 1 << 16):
+        host = rng.integers(0, 256, (n, 160), dtype=np.uint8)
+        host[:, 0:4] = (1, 0, 0, 0)  # HandshakeInit
+        host[:, L - 16:L] = 0        # no mac2
+        for row in host:             # a valid mac1: an overloaded message takes the filter's whole path
+            row[L - 32:L - 16] = np.frombuffer(
+                hashlib.blake2s(row[:L - 32].tobytes(), key=mac1_key, digest_size=16).digest(), np.uint8)
+        desc = np.zeros(n, DESC_DTYPE)
+        desc["offset"], desc["len"] = np.arange(n, dtype=np.uint64) * 160, L
+        buf, d = dev(host.reshape(-1)), dev(desc.view(np.uint8).reshape(-1, 16))
+        nonces = dev(rng.integers(0, 256, (n, 24), dtype=np.uint8))
+        replies, st, flags, counts = z(n, 64), z(n), z(n), z(n, dtype=torch.int32)
+        ws = ratelimit.rate_workspace(eng, n)
+        row = {}
+        for sources in (1, 256, 20000):
+            pool = np.zeros((sources, 24), np.uint8)
+            pool[:, 0] = 10
+            pool[:, 1:4] = (np.arange(sources)[:, None] >> (16, 8, 0)) & 255  # 10.x.y.z
+            addrs = dev(pool[np.arange(n) % sources])
+            count = lambda: ratelimit.count_dev(eng, T, d, addrs, buf, flags, counts, workspace=ws)  # noqa: E731
+            res = {"rate_count": measure(count, empty)}
+            over = int(flags.sum())
+            true_over = sum(max(0, (n - s + sources - 1) // sources - ratelimit.RATE_LIMIT) for s in range(min(sources, n)))
+            assert over >= true_over  # a count-min estimate is never below the true count
+            res["messages_over_the_limit"], res["by_their_true_counts"] = over, true_over
+            res["cookie_reply_with_the_flags"] = measure(
+                lambda: eng.cookie_reply_dev(keys, d, addrs, flags, nonces, buf, replies, st), lambda: None)
+            assert int((st == aead.PKT_COOKIE).sum()) == over and int((st == aead.PKT_OK).sum()) == n - over
+            res["cookie_reply_all_overloaded"] = measure(
+                lambda: eng.cookie_reply_dev(keys, d, addrs, None, nonces, buf, replies, st), lambda: None)
+            row[f"sources_{sources}"] = res
+        out[f"messages_{n}"] = row
+    # Where the count's time goes: the same 320 Ki items (64 Ki messages x 5, the last batch above) grouped with
+    # two radix passes (the default sketch), one (51 x 5 = 255 buckets) and none (one bucket: 320 Ki messages on a
+    # 1 x 1 sketch, descriptors and addresses repeated); the kernels around the passes are the same in all three.
+    n, split = 1 << 16, {}
+    for label, width, depth, reps in (("two_radix_passes_5437x5", T.width, T.depth, 1), ("one_radix_pass_51x5", 51, 5, 1),
+                                      ("no_radix_pass_1x1", 1, 1, 5)):
+        S = ratelimit.RateTables(eng, width, depth)
+        S.seeds.copy_(seeds[:depth])
+        m = n * reps
+        d_m, addrs_m, flags_m = d.repeat(reps, 1), addrs.repeat(reps, 1), z(m)
+        ws_m = ratelimit.rate_workspace(eng, m, width, depth)
+        assert m * depth == n * T.depth
+        split[label] = measure(lambda: ratelimit.count_dev(eng, S, d_m, addrs_m, buf, flags_m, workspace=ws_m),
+                               lambda: S.buckets.zero_())
+    out["where_the_time_goes_320Ki_items"] = split
+    d_now, reset_out = dev(np.array([10**12], np.int64)), z(1, dtype=torch.int32)
+    turn = lambda: ratelimit.turn_dev(eng, T, d_now, new_seeds, reset_out)  # noqa: E731
+    out["rate_turn_with_reset"] = measure(turn, lambda: T.last_reset_ns.zero_())
+    assert int(reset_out[0]) == 1
+    out["rate_turn_without_reset"] = measure(turn, lambda: None)
+    assert int(reset_out[0]) == 0
+    out["note"] = ("stream events around one call each, medians of 7 repetitions after one warm-up; rate_count = key + "
+                   "2 x (hist + scan + scatter) + reduce + carry + verdict + finish kernels over n * depth items from an "
+                   "empty sketch; the sources are dealt round-robin; cookie_reply = rg_cookie_reply_batch_dev on the "
+                   "same batch (valid mac1, no mac2) with overload = the count's flags and with overload = NULL; "
+                   "rate_turn = decide + wipe kernels")
+    with open(os.path.join(root, "profiles", "ratelimit_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate", "session", "timers", "pending"]
+                            "peerstate", "session", "timers", "pending", "ratelimit"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
                       ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg),
-                      ("timers", timers_leg), ("pending", pending_leg)):
+                      ("timers", timers_leg), ("pending", pending_leg), ("ratelimit", ratelimit_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
