@@ -818,8 +818,8 @@ int rg_recv_batch_dev_finish(rg_sessions *s, const uint64_t *src, uint8_t *statu
  * with the other device calls: the one-stream rule above applies (a call on another stream while the
  * context's last batch is in flight fails with RG_EINVAL, nothing enqueued), and a buffer of the context
  * that has to grow does so outside a stream capture (run the shape once before capturing it).  The endpoint
- * side effect of decrypt_packet (lib.rs:670-679) stays with the caller, which reads status and key_idx_out
- * when it chooses to; the keepalive side effect (:664-669) is rg_timer_note_recv_batch_dev behind this call.
+ * side effect of decrypt_packet (lib.rs:670-679) is rg_endpoint_note_recv_batch_dev behind this call, on its
+ * status and key_idx_out; the keepalive side effect (:664-669) is rg_timer_note_recv_batch_dev, likewise.
  *
  * n == 0 returns RG_OK.  RG_EINVAL, nothing enqueued: a null required pointer (undo, counters_out and
  * key_idx_out are optional), n > 2^32 - 1, windows not 8-byte or workspace not 16-byte aligned,
@@ -1174,7 +1174,8 @@ typedef struct rg_session_timer {    /* 16 bytes, 8-byte aligned */
  * Unlike the reference: a peer gets at most one keepalive a turn, decided on the state before the turn (the
  * reference pops entries in time order, ties arbitrary, so two pending sessions of one peer yield one keepalive or
  * two); a row holds one RekeyAttempt entry (the reference pushes one per send past REKEY_AFTER_MESSAGES);
- * endpoints stay with the caller. */
+ * endpoints are the peer-endpoint section's: rg_endpoint_gate_batch_dev on ka_slots_out, rg_endpoint_peers_batch_dev
+ * on rekey_peers_out. */
 size_t rg_timer_workspace_size(size_t nkeys, size_t npeers);
 int rg_timer_arm_batch_dev(rg_ctx *ctx, rg_session_timer *timers, uint32_t nkeys, const uint32_t *rows /* [n] */,
                            const uint8_t *gate /* [n] or NULL */, size_t n, const uint64_t *now_ns,
@@ -1297,7 +1298,8 @@ typedef struct rg_pending_tables {
  * 5 s retry governs -- otherwise a batch of packets a millisecond later would replace the handshake before its
  * response can arrive.  (b) The timers are evaluated statelessly on {started_ns, sent_ns}, not popped from a heap;
  * the same entries fire: InitAttempt at sent + 5 s, ExpireHandshake at sent + 90 s, and no retry once
- * now >= started + 90 s.  (c) Session ids, esk, timestamps and endpoints stay the caller's. */
+ * now >= started + 90 s.  (c) Session ids, esk and timestamps stay the caller's;
+ * endpoints are the peer-endpoint section's (rg_endpoint_peers_batch_dev on init_peers_out). */
 size_t rg_pending_workspace_size(size_t n, size_t m, uint32_t npeers);
 int rg_pending_index_dev(rg_ctx *ctx, const rg_pending_tables *tables, void *stream);
 int rg_pending_install_batch_dev(rg_ctx *ctx, const rg_pending_tables *tables, rg_hs_pending *batch /* [n] */,
@@ -1395,6 +1397,90 @@ int rg_rate_count_batch_dev(rg_ctx *ctx, const rg_rate_tables *tables, const rg_
 int rg_rate_turn_dev(rg_ctx *ctx, const rg_rate_tables *tables, const uint64_t *now_ns, uint64_t period_ns,
                      const rg_rate_seed *new_seeds /* [depth], caller's CSPRNG */, uint32_t *reset_out /* [1] */,
                      void *stream);
+
+/* ------------------------------ device-resident peer endpoints (batch, async) */
+/* PeerState.endpoint (rustyguard-core/src/lib.rs:160-181) on the stream that sends and receives: where each peer's
+ * packets last came from, moved only by what was authenticated, and handed to the next send as a destination array.
+ * The reference moves it in decrypt_packet for every data packet that is authenticated and passes anti-replay
+ * (lib.rs:659-671; keepalives count, a forged or replayed packet does not -- its test
+ * forged_packet_does_not_update_peer_endpoint) and in handle_handshake_resp for the response that finishes a pending
+ * handshake (handshake.rs:205); handle_handshake_init does not touch it.  It reads it in send_message (lib.rs:550-553:
+ * a peer without one is Error::Rejected before anything is encrypted) and for keepalives and rekey initiations
+ * (time.rs:67, :135).  With these calls receive -> note -> ... -> gate -> send is one chain with no host read, and the
+ * output of a turn is frames plus a destination address array.
+ *
+ * The conventions are the peer-state and session sections': every pointer is device memory; the calls enqueue on
+ * `stream` and return without waiting, allocate nothing and keep nothing in the context (so they can be captured
+ * into a graph; no memset node); n == 0 returns RG_OK; RG_EINVAL with nothing enqueued -- and before the device is
+ * touched at all -- for a null pointer (every array is required), n > 2^32 - 1 or a misaligned array (endpoints 16
+ * bytes; rg_src_addr rows 8; word arrays 4).  A lane stores what it decides after everything else it writes.  No
+ * index reaches memory unchecked.  Nothing is decided by the order the lanes arrive in.
+ *
+ * One rg_endpoint row runs parallel to every rg_hs_peer row; the caller owns the array.  A zeroed row is None, and
+ * the configured endpoint of a peer (PeerState::new(p.endpoint)) is stored by the caller before the first call.  A
+ * row counts as Some when `set` is not 0.  Addresses come in and go out as rg_src_addr, of which the first 18 bytes
+ * are meaningful; every rg_src_addr these calls write has `pad` zero, so the same arrays feed the filter and the rate
+ * limiter. */
+typedef struct rg_endpoint {         /* 32 bytes, rows 16-byte aligned; zeroed = None */
+    uint8_t  ip[16];                 /* rg_src_addr's encoding */
+    uint16_t port_le;
+    uint16_t set;                    /* 0 = None, 1 = Some; nothing else is ever written */
+    uint8_t  zero[12];               /* always written as zero */
+} rg_endpoint;
+
+/* The three note calls change the table.  Each equals this loop, bit for bit on every byte of endpoints:
+ *   for i in array order:
+ *     status[i] == RG_PKT_OK and p = peer_of(i) < npeers -> endpoints[p] = { src[i].ip, src[i].port_le, 1, zeros }
+ * and every other row keeps its bytes.  They differ in peer_of alone:
+ *   rg_endpoint_note_recv_batch_dev    runs behind rg_recv_batch_dev_resident on its key_idx_out and status and IN FRONT
+ *                                      OF rg_route_check_batch_dev (the reference has moved the endpoint before the
+ *                                      source check, and the check overwrites RG_PKT_OK):
+ *                                      peer_of(i) = slot_peer[key_idx[i]] when key_idx[i] < nkeys, none otherwise; a
+ *                                      free row (RG_PEER_NONE) names no peer
+ *   rg_endpoint_note_peers_batch_dev   peer_of(i) = peer_idx[i]
+ *   rg_endpoint_note_finish_batch_dev  runs behind rg_handshake_finish_batch_dev on its pend_idx_out and status:
+ *                                      peer_of(i) = pend_peers[pend_idx_out[i]] when pend_idx_out[i] < npending
+ * computed with atomicMax(claim[p], i + 1) -- reduced within each wave first, so a batch of one session costs one
+ * atomic a wave -- and a commit in which the lane whose i + 1 is the claim stores the row and then puts the claim
+ * word back to 0.  claim is npeers words the caller zeroes ONCE; every call leaves it zeroed, no fill is enqueued and
+ * the cost follows n, not npeers.  A claim array that is not zero makes the call skip peers; it stays memory-safe (the
+ * claim word is compared, never used as an index).  claim belongs to one call at a time.
+ *
+ * The two gather calls only read the table, one lane per item:
+ *   rg_endpoint_gate_batch_dev   runs in front of rg_send_batch_dev_resident, behind rg_route_batch_dev or on
+ *                                rg_timer_turn_dev's ka_slots_out.  If slots[i] < nkeys, p = slot_peer[slots[i]] <
+ *                                npeers and endpoints[p] is Some: slots_out[i] = slots[i], dst_out[i] = the address
+ *                                with pad zero.  Otherwise slots_out[i] = RG_KEY_SKIP and dst_out[i] is 24 zero bytes;
+ *                                the send then reports RG_PKT_REJECTED, takes no counter and leaves the frame alone,
+ *                                which is send_message's early return.  slots_out may be slots.
+ *   rg_endpoint_peers_batch_dev  the same by peer with RG_PEER_NONE as the "no" value, for the rekey and pending
+ *                                lists that feed rg_peer_cookies_batch_dev -> rg_handshake_initiate_batch_dev ->
+ *                                rg_peer_mac1_batch_dev, which take a RG_PEER_NONE row as it is.  peers_out may be
+ *                                peer_idx.
+ *
+ * Unlike the reference: (a) a keepalive or rekey for a peer without an endpoint is skipped, where time.rs:67 and :135
+ * `expect` one; (b) the claim and commit replace arrival order: the last eligible item in ARRAY order wins, which is
+ * the in-order loop's result whatever order the lanes run in. */
+int rg_endpoint_note_recv_batch_dev(rg_ctx *ctx, rg_endpoint *endpoints, uint32_t npeers,
+                                    const uint32_t *slot_peer /* [nkeys] */, uint32_t nkeys,
+                                    const uint32_t *key_idx /* [n] */, const uint8_t *status /* [n] */,
+                                    const rg_src_addr *src /* [n] */, size_t n, uint32_t *claim /* [npeers] */,
+                                    void *stream);
+int rg_endpoint_note_peers_batch_dev(rg_ctx *ctx, rg_endpoint *endpoints, uint32_t npeers,
+                                     const uint32_t *peer_idx /* [n] */, const uint8_t *status /* [n] */,
+                                     const rg_src_addr *src /* [n] */, size_t n, uint32_t *claim /* [npeers] */,
+                                     void *stream);
+int rg_endpoint_note_finish_batch_dev(rg_ctx *ctx, rg_endpoint *endpoints, uint32_t npeers,
+                                      const uint32_t *pend_idx_out /* [n] */, const uint32_t *pend_peers /* [npending] */,
+                                      uint32_t npending, const uint8_t *status /* [n] */,
+                                      const rg_src_addr *src /* [n] */, size_t n, uint32_t *claim /* [npeers] */,
+                                      void *stream);
+int rg_endpoint_gate_batch_dev(rg_ctx *ctx, const rg_endpoint *endpoints, uint32_t npeers,
+                               const uint32_t *slot_peer /* [nkeys] */, uint32_t nkeys, const uint32_t *slots /* [n] */,
+                               size_t n, uint32_t *slots_out /* [n] */, rg_src_addr *dst_out /* [n] */, void *stream);
+int rg_endpoint_peers_batch_dev(rg_ctx *ctx, const rg_endpoint *endpoints, uint32_t npeers,
+                                const uint32_t *peer_idx /* [n] */, size_t n, uint32_t *peers_out /* [n] */,
+                                rg_src_addr *dst_out /* [n] */, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

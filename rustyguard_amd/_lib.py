@@ -155,6 +155,12 @@ SIGNATURES = {
     "rg_rate_count_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_vp, c_size, c_vp, c_size, c_u32, c_vp, c_vp, c_vp, c_size,
                                         c_vp]),
     "rg_rate_turn_dev": (c_int, [c_vp, c_vp, c_vp, c_u64, c_vp, c_vp, c_vp]),
+    "rg_endpoint_note_recv_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
+    "rg_endpoint_note_peers_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_size, c_vp, c_vp]),
+    "rg_endpoint_note_finish_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp, c_size, c_vp,
+                                                  c_vp]),
+    "rg_endpoint_gate_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_size, c_vp, c_vp, c_vp]),
+    "rg_endpoint_peers_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_size, c_vp, c_vp, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

@@ -68,6 +68,12 @@
          batch beside it (fed the count's flags, and all overloaded), and rg_rate_turn_dev with and without a
          reset.  Medians of seven with min-max, by stream events.  Also written to profiles/ratelimit_bench.json
 
+  endpoint  the device-resident peer endpoints on cfg2, cfg4 and 1 Ki packets of one session: the resident receive
+         + rg_timer_note_recv_batch_dev with and without rg_endpoint_note_recv_batch_dev, the resident send with and
+         without rg_endpoint_gate_batch_dev, the note, the gate and the timer note each alone, by stream events,
+         medians of seven with min-max; and by host wall clock the read-back and numpy last-per-peer a caller does
+         today.  Also written to profiles/endpoint_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -1389,15 +1395,150 @@ def ratelimit_leg(eng):
     return out
 
 
+def endpoint_leg(eng):
+    """The device-resident peer endpoints on the replay and send legs' two workloads (cfg2: 64 Ki x 1500 B on one
+    session; cfg4: 256 sessions x 4 Ki x 1500 B interleaved) and on 1 Ki packets of one session (the launch floor),
+    peer = session, all in one run: (a) the resident receive + rg_timer_note_recv_batch_dev, (b) the same with
+    rg_endpoint_note_recv_batch_dev, (c) the resident send, (d) rg_endpoint_gate_batch_dev + the resident send, (e)
+    the note, the gate and rg_timer_note_recv_batch_dev each alone on the same batch -- by stream events, medians of
+    seven with min-max -- and, by host wall clock, what a caller does today behind the same receive: status and
+    key_idx_out to pinned memory, a stream synchronise and a vectorised numpy last-per-peer.  Written to
+    profiles/endpoint_bench.json."""
+    import time
+
+    from rustyguard_amd import endpoint, timers
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(83)
+    T0 = 10**12
+    d_now = torch.from_numpy(np.array([T0], np.int64)).cuda()
+
+    def shape(w):
+        n, nk = w.n, len(w.receivers)
+        b = DeviceBatch(eng, w)
+        b.fill()
+        plain = b.buf.clone()
+        b.seal()
+        sealed = b.buf.clone()
+        table = torch.from_numpy(aead.rx_table(w.receivers, np.arange(nk, dtype=np.uint32))).cuda()
+        ws_r, ws_s = eng.replay_workspace(n, nk), eng.send_workspace(n, nk)
+        win = torch.zeros(nk * 33, dtype=torch.int64, device="cuda")
+        state = torch.zeros(nk * 3, dtype=torch.int64, device="cuda")
+        tm = timers.timer_rows(eng, nk)
+        host_slot_peer = np.arange(nk, dtype=np.uint32)  # peer = session
+        slot_peer = torch.from_numpy(host_slot_peer.view(np.int32).copy()).cuda()
+        E = endpoint.EndpointTable(eng, nk)
+        host_src = np.zeros((n, 24), np.uint8)
+        host_src[:, :18] = rng.integers(0, 256, (n, 18), dtype=np.uint8)
+        src = torch.from_numpy(host_src).cuda()
+        key_idx = torch.zeros(n, dtype=torch.int32, device="cuda")
+        slots = torch.from_numpy(np.ascontiguousarray(w.desc["key_idx"], np.uint32).view(np.int32).copy()).cuda()
+        slots_out, dst = torch.zeros(n, dtype=torch.int32, device="cuda"), torch.zeros((n, 24), dtype=torch.uint8, device="cuda")
+        st_send = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        pin_st, pin_k = torch.empty(n, dtype=torch.uint8).pin_memory(), torch.empty(n, dtype=torch.int32).pin_memory()
+        host_ep = np.zeros((nk, 24), np.uint8)
+
+        def recv():
+            eng.recv_batch_dev_resident(b.keys, table, win, b.desc_open, b.buf, b.status, key_idx_out=key_idx,
+                                        workspace=ws_r)
+
+        def timer_note():
+            timers.note_recv_batch_dev(eng, tm, state, key_idx, b.status, d_now)
+
+        def ep_note():
+            E.note_recv_batch_dev(slot_peer, key_idx, b.status[:n], src)
+
+        def gate():
+            E.gate_batch_dev(slot_peer, slots, slots_out, dst)
+
+        def send(sl):
+            eng.send_batch_dev_resident(b.keys, b.receivers, state, sl, b.desc_seal, b.buf, st_send, workspace=ws_s)
+
+        def today():
+            recv()
+            pin_st.copy_(b.status[:n], non_blocking=True)
+            pin_k.copy_(key_idx, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            idx = np.nonzero(pin_st.numpy() == 0)[0]
+            last = np.full(nk, -1, np.int64)
+            last[host_slot_peer[pin_k.numpy().view(np.uint32)[idx]]] = idx  # repeated peers: the last index stays
+            moved = last >= 0
+            host_ep[moved] = host_src[last[moved]]
+
+        def restore_recv():
+            b.buf.copy_(sealed)
+            win.zero_()
+            tm.zero_()
+            torch.cuda.synchronize()
+
+        def restore_send():
+            b.buf.copy_(plain)
+            state.zero_()
+            torch.cuda.synchronize()
+
+        def gpu_ms(fn):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            z.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(z)
+
+        def wall_ms(fn):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        legs = (("a_recv_timer_note_gpu_ms", restore_recv, gpu_ms, lambda: (recv(), timer_note())),
+                ("b_recv_timer_note_endpoint_note_gpu_ms", restore_recv, gpu_ms, lambda: (recv(), timer_note(), ep_note())),
+                ("c_send_gpu_ms", restore_send, gpu_ms, lambda: send(slots)),
+                ("d_gate_send_gpu_ms", restore_send, gpu_ms, lambda: (gate(), send(slots_out))),
+                ("e_endpoint_note_alone_gpu_ms", lambda: None, gpu_ms, ep_note),
+                ("e_endpoint_gate_alone_gpu_ms", lambda: None, gpu_ms, gate),
+                ("e_timer_note_alone_gpu_ms", lambda: None, gpu_ms, timer_note),
+                ("caller_today_recv_readback_numpy_wall_ms", restore_recv, wall_ms, today),
+                ("resident_recv_notes_wall_ms", restore_recv, wall_ms, lambda: (recv(), timer_note(), ep_note())))
+        t = {name: [] for name, *_ in legs}
+        for rep in range(9):
+            for name, restore, clock, fn in legs:
+                restore()
+                t[name].append(clock(fn))
+                if name.startswith("b_"):
+                    assert (b.status[:n] == 0).all().item() and not E.claim.any().item()
+                if name.startswith("d_"):
+                    assert (st_send == 0).all().item() and torch.equal(slots_out, slots)
+        r = {k: {"median": round(float(np.median(v[2:])), 4), "min": round(min(v[2:]), 4), "max": round(max(v[2:]), 4)}
+             for k, v in t.items()}
+        # the device table and the caller's host map hold the same addresses
+        rows = E.endpoints.cpu().numpy()
+        assert np.array_equal(rows[:, :18], host_ep[:, :18]) and (rows[:, 18] == 1).all()
+        return {"packets": n, "sessions": nk, **r}
+
+    res = {"cfg2": shape(workloads.build("cfg2")), "cfg4": shape(workloads.build("cfg4")),
+           "one_session_1024": shape(workloads.uniform(1024, name="1ki")),
+           "note": "9 alternating repetitions, the first two dropped; frames, windows, timers and send state restored "
+                   "outside the timed region; peer = session, every packet authentic; *_gpu_ms by stream events around "
+                   "the calls named, *_wall_ms by host wall clock around the calls and a device sync; the (e) calls run "
+                   "on the key_idx_out and status the receive before them left; caller_today = the same receive, then "
+                   "status and key_idx_out to pinned memory, a stream synchronise and a numpy last-per-peer into a "
+                   "host address map"}
+    with open(os.path.join(root, "profiles", "endpoint_bench.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    return res
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate", "session", "timers", "pending", "ratelimit"]
+                            "peerstate", "session", "timers", "pending", "ratelimit", "endpoint"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
                       ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg),
-                      ("timers", timers_leg), ("pending", pending_leg), ("ratelimit", ratelimit_leg)):
+                      ("timers", timers_leg), ("pending", pending_leg), ("ratelimit", ratelimit_leg),
+                      ("endpoint", endpoint_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
