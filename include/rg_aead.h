@@ -639,7 +639,8 @@ int rg_host_unregister(void *p);
 
 /* ------------------------- per-message drop-in for CryptoPrimatives */
 /* Exactly Core::chacha20poly1305_enc / _dec (prim.rs:179-201): any nonce,
- * any AAD, any length, host pointers, blocking.  dec returns RG_OK, or
+ * any AAD, any length up to RFC 8439's 64 * (2^32 - 1) bytes (a longer
+ * one is RG_EINVAL), host pointers, blocking.  dec returns RG_OK, or
  * RG_PKT_DECRYPT_ERR (positive 1) on a tag mismatch with payload untouched. */
 int rg_chacha20poly1305_enc(rg_ctx *ctx, const uint8_t key[32], const uint8_t nonce[12], const uint8_t *aad,
                             size_t aad_len, uint8_t *payload, size_t len, uint8_t tag[16]);

@@ -12,7 +12,9 @@ static int general_one(rg_ctx *ctx, bool dec, const uint8_t key[32], const uint8
     if (rc) return rc;
     if (!key || !nonce || !tag || (aad_len && !aad) || (len && !payload))
         return set_err(RG_EINVAL, "aead: bad args");
-    if (len > (64ull << 32)) return set_err(RG_EINVAL, "aead: message too long for a 32-bit block counter");
+    // chunk c takes block counter c + 1 and counter 0 is the Poly1305 key block: 2^32 - 1 chunks at the most
+    // (RFC 8439 §2.8), or the last chunk's counter would wrap onto it
+    if (len > 64ull * 0xFFFFFFFFull) return set_err(RG_EINVAL, "aead: message too long for a 32-bit block counter");
     std::lock_guard<std::mutex> g(ctx->mu);
     // one pinned image of the device arena: the inputs are packed into it on the host, moved by one
     // H2D copy, and the results come back by one D2H copy (pageable copies of each piece cost tens of

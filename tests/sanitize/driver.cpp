@@ -9,10 +9,13 @@
 //   4 a group's session table (rg_sessions_create_group)
 //   5 device-frame sessions: rg_send_batch_dev / rg_recv_batch_dev + _finish (device memory = host here)
 //   6 fail-closed paths: a lost planner hand-off (test hook) and lost completions (bounded waits)
-//   7 the per-message drop-in (rg_chacha20poly1305_enc/dec)
+//   7 the per-message drop-in (rg_chacha20poly1305_enc/dec and the XChaCha pair): a short message, then the
+//     lengths of tests/message_cases.py's call sequence on exact-size heap buffers, and the argument refusals
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <random>
 #include <vector>
 
@@ -291,6 +294,77 @@ static void scenario_per_message(rg_ctx *c) {
     CHECK(memcmp(msg, before, 100) == 0, "forged message untouched");
 }
 
+// One seal -> forged open -> open on heap buffers of exactly aad_len and len bytes, so that a read or write
+// of the caller's memory past either (the host packs both into 16-byte padded slots) is an ASan report.
+// len 0 goes with a null payload, aad_len 0 with a non-null pointer to no bytes.
+static void message_round_trip(rg_ctx *c, bool x, size_t aad_len, size_t len) {
+    auto enc = x ? rg_xchacha20poly1305_enc : rg_chacha20poly1305_enc;
+    auto dec = x ? rg_xchacha20poly1305_dec : rg_chacha20poly1305_dec;
+    std::unique_ptr<uint8_t[]> aad(new uint8_t[aad_len]), msg(len ? new uint8_t[len] : nullptr);
+    std::unique_ptr<uint8_t[]> key(new uint8_t[32]), nonce(new uint8_t[x ? 24 : 12]), tag(new uint8_t[16]);
+    for (size_t i = 0; i < aad_len; ++i) aad[i] = (uint8_t)(7 * i + 1);
+    for (size_t i = 0; i < len; ++i) msg[i] = (uint8_t)(i ^ (i >> 8) ^ (i >> 16));
+    for (int i = 0; i < 32; ++i) key[i] = (uint8_t)(5 * i + len);
+    for (int i = 0; i < (x ? 24 : 12); ++i) nonce[i] = (uint8_t)(0xF0 + i);
+    const std::vector<uint8_t> plain(msg.get(), msg.get() + len);
+    CHECK(enc(c, key.get(), nonce.get(), aad.get(), aad_len, msg.get(), len, tag.get()) == RG_OK, "enc %zu/%zu", aad_len, len);
+    const std::vector<uint8_t> sealed(msg.get(), msg.get() + len);
+    if (len >= 16) CHECK(sealed != plain, "enc changed the text %zu/%zu", aad_len, len);
+    tag[15] ^= 0x80;
+    CHECK(dec(c, key.get(), nonce.get(), aad.get(), aad_len, msg.get(), len, tag.get()) == RG_PKT_DECRYPT_ERR,
+          "forged %zu/%zu", aad_len, len);
+    CHECK(std::equal(sealed.begin(), sealed.end(), msg.get()), "forged message untouched %zu/%zu", aad_len, len);
+    tag[15] ^= 0x80;
+    if (aad_len) {
+        aad[aad_len - 1] ^= 1;
+        CHECK(dec(c, key.get(), nonce.get(), aad.get(), aad_len, msg.get(), len, tag.get()) == RG_PKT_DECRYPT_ERR,
+              "forged aad %zu/%zu", aad_len, len);
+        aad[aad_len - 1] ^= 1;
+    }
+    CHECK(dec(c, key.get(), nonce.get(), aad.get(), aad_len, msg.get(), len, tag.get()) == RG_OK, "dec %zu/%zu", aad_len, len);
+    CHECK(std::equal(plain.begin(), plain.end(), msg.get()), "dec restored the text %zu/%zu", aad_len, len);
+}
+
+// the lengths of tests/message_cases.py SEQUENCES, in its order (long first, short after long, the regrow),
+// on the context whose arena scenario_per_message left small; then the argument refusals
+static void scenario_per_message_long(rg_ctx *c) {
+    const struct {
+        bool x;
+        size_t aad_len, len;
+    } seq[] = {{false, 145, 12289}, {false, 1, 1},   {false, 0, 0},    {false, 4097, 17}, {false, 0, 4097},
+               {false, 16, 65553},  {true, 15, 15},  {false, 32, 4097}, {true, 4097, 65553}, {true, 0, 0}};
+    for (const auto &s : seq) message_round_trip(c, s.x, s.aad_len, s.len);
+    // refusals come before any allocation or copy: a 1-byte buffer behind a length past the limit is not read
+    std::unique_ptr<uint8_t[]> one(new uint8_t[1]), key(new uint8_t[32]), nonce(new uint8_t[24]), tag(new uint8_t[16]);
+    one[0] = 0x5A;
+    memset(key.get(), 1, 32);
+    memset(nonce.get(), 2, 24);
+    memset(tag.get(), 3, 16);
+    // 64 * (2^32 - 1) bytes is the most the 32-bit block counter covers (counter 0 is the Poly1305 key block)
+    const size_t too_longs[2] = {(64ull << 32) + 1, 64ull * 0xFFFFFFFFull + 1};
+    int (*const encs[2])(rg_ctx *, const uint8_t *, const uint8_t *, const uint8_t *, size_t, uint8_t *, size_t, uint8_t *) = {
+        rg_chacha20poly1305_enc, rg_xchacha20poly1305_enc};
+    int (*const decs[2])(rg_ctx *, const uint8_t *, const uint8_t *, const uint8_t *, size_t, uint8_t *, size_t,
+                         const uint8_t *) = {rg_chacha20poly1305_dec, rg_xchacha20poly1305_dec};
+    for (int x = 0; x < 2; ++x) {
+        for (const size_t too_long : too_longs) {
+            CHECK(encs[x](c, key.get(), nonce.get(), nullptr, 0, one.get(), too_long, tag.get()) == RG_EINVAL, "enc too long");
+            CHECK(decs[x](c, key.get(), nonce.get(), nullptr, 0, one.get(), too_long, tag.get()) == RG_EINVAL, "dec too long");
+        }
+        CHECK(encs[x](c, nullptr, nonce.get(), nullptr, 0, one.get(), 1, tag.get()) == RG_EINVAL, "null key");
+        CHECK(encs[x](c, key.get(), nullptr, nullptr, 0, one.get(), 1, tag.get()) == RG_EINVAL, "null nonce");
+        CHECK(encs[x](c, key.get(), nonce.get(), nullptr, 0, one.get(), 1, nullptr) == RG_EINVAL, "null tag");
+        CHECK(decs[x](c, key.get(), nonce.get(), nullptr, 0, one.get(), 1, nullptr) == RG_EINVAL, "dec null tag");
+        CHECK(encs[x](c, key.get(), nonce.get(), nullptr, 3, one.get(), 1, tag.get()) == RG_EINVAL, "null aad with a length");
+        CHECK(decs[x](c, key.get(), nonce.get(), nullptr, 3, one.get(), 1, tag.get()) == RG_EINVAL, "dec null aad");
+        CHECK(encs[x](c, key.get(), nonce.get(), nullptr, 0, nullptr, 1, tag.get()) == RG_EINVAL, "null payload with a length");
+    }
+    bool tag_kept = true;
+    for (int i = 0; i < 16; ++i) tag_kept = tag_kept && tag[i] == 3;
+    CHECK(one[0] == 0x5A && tag_kept, "a refused call touched nothing");
+    message_round_trip(c, false, 5, 100); // and the context still works
+}
+
 int main() {
     std::mt19937_64 rng(12345);
     rg_ctx *c = nullptr;
@@ -301,6 +375,7 @@ int main() {
     scenario_device_sessions(c, rng);
     scenario_failclosed(c, rng);
     scenario_per_message(c);
+    scenario_per_message_long(c);
     rg_destroy(c);
     scenario_group(rng);
     if (g_fail) {

@@ -1201,10 +1201,16 @@ def test_per_message_key_wiped_from_device():
         engine.chacha20poly1305_dec(key, aead.nonce(9), b"aad", msg, bytes(16))
     xt = engine.xchacha20poly1305_enc(key, bytes(24), b"", msg)
     engine.xchacha20poly1305_dec(key, bytes(24), b"", msg, xt)
+    # one long call (AAD 145, text 12289: three rounds of the kernel's lanes) regrows the arena past its
+    # first 4 KiB; the read-back covers the whole grown arena (job, padded AAD, padded text, tag)
+    long_msg = bytearray(b"\xa5" * 12289)
+    engine.chacha20poly1305_enc(key, aead.nonce(10), b"\x11" * 145, long_msg)
+    grown = 160 + 12304 + 16  # without the job in front of them
     out = (ctypes.c_uint8 * (1 << 16))()
     got = _lib.check(engine.library.rg_debug_read_arena(engine.handle, 0, out, len(out)), "rg_debug_read_arena",
                      engine.library)
     assert got > 0
+    assert grown < got < len(out)  # the arena grew, and the buffer took all of it
     arena = bytes(out[:got])
     for w in range(0, 32, 8):  # no 8-byte run of the key anywhere
         assert key[w:w + 8] not in arena
