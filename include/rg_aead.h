@@ -95,7 +95,8 @@ enum rg_pkt_status {
                                the handshake calls) */
     RG_PKT_UNROUTABLE = 9,  /* cryptokey routing (rg_route_batch_dev, rg_route_check_batch_dev): the inner address
                                matches no allowed prefix, or on receive a prefix of another peer */
-    RG_PKT_FULL = 10,       /* rg_session_install_batch_dev: the session table has no free row left */
+    RG_PKT_FULL = 10,       /* rg_session_install_batch_dev: the session table has no free row left;
+                               rg_demux_batch_dev: the message's list has no row left */
 };
 
 /* Statuses fail closed.  A packet reads RG_PKT_OK only after the kernel that processed it wrote that
@@ -1482,6 +1483,110 @@ int rg_endpoint_gate_batch_dev(rg_ctx *ctx, const rg_endpoint *endpoints, uint32
 int rg_endpoint_peers_batch_dev(rg_ctx *ctx, const rg_endpoint *endpoints, uint32_t npeers,
                                 const uint32_t *peer_idx /* [n] */, size_t n, uint32_t *peers_out /* [n] */,
                                 rg_src_addr *dst_out /* [n] */, void *stream);
+
+/* ------------------------------ device-resident inbound demultiplexer (batch, async) */
+/* The `match msg_type` of Sessions::recv_message (rustyguard-core/src/lib.rs:605-630) on the stream that runs the
+ * chains behind it: one array of datagrams in arrival order -- what recvmmsg hands a node, message types 1-4 and junk
+ * interleaved -- is split into the descriptor lists the existing calls take as they are, and the chains' verdicts are
+ * carried back to the datagrams' own order.  With these two calls a mixed batch goes from one descriptor array to its
+ * final per-datagram statuses with no host read in between:
+ *   rg_demux_batch_dev -> handshake list: rg_rate_count_batch_dev -> rg_cookie_reply_batch_dev (over hs_desc, hs_addrs)
+ *                                         -> rg_handshake_init_batch_dev (over init_desc, gate = the filter's status)
+ *                                         -> rg_handshake_finish_batch_dev (over resp_desc, the same gate)
+ *                      -> cookie list:    rg_peer_cookie_consume_batch_dev (over ck_desc)
+ *                      -> data list:      rg_recv_batch_dev_resident -> rg_endpoint_note_recv_batch_dev (data_addrs)
+ *   -> rg_demux_verdict_batch_dev
+ *
+ * The conventions are the peer-state, session and endpoint sections': every array is device memory; the calls enqueue
+ * on `stream` and return without waiting, allocate nothing and keep nothing in the context (so they can be captured
+ * into a graph; every fill is a kernel, no memset node); every scratch array lives in `workspace`, 16-byte aligned
+ * and at least rg_demux_workspace_size(n) bytes (0 for n > 2^32 - 1), which belongs to one call at a time; n == 0
+ * returns RG_OK with nothing written; RG_EINVAL with nothing enqueued -- and before the device is touched at all --
+ * for a null required pointer (the arrays of a list whose capacity is 0 may be NULL), n > 2^32 - 1, a misaligned
+ * array (rg_pkt_desc rows and the workspace 16 bytes; rg_src_addr rows 8; buf, pos and counts 4) or a short workspace.
+ * Nothing is decided by the order the lanes arrive in: there is no atomic.  buf is never written.  A lane stores
+ * status[i] after everything else it writes.  No index reaches memory unchecked.
+ *
+ * Three lists, because that is how the existing calls consume them.  The handshake list holds types 1 and 2 together
+ * in array order: rg_rate_count_batch_dev and rg_cookie_reply_batch_dev both take mixed 148 / 92-byte messages, and the
+ * sketch's result depends on the array order of every handshake message of a source (the reference calls overloaded()
+ * in handle_handshake_init and handle_handshake_resp alike, handshake.rs:47, :151).  It is four parallel arrays of
+ * cap_hs rows: hs_desc, every listed message; hs_addrs, their source addresses with `pad` zeroed; init_desc, row k =
+ * hs_desc[k] if the message is type 1, else the inert row; resp_desc, the same for type 2.  Because the four are
+ * parallel, the filter's status array over hs_desc is, unchanged, the `gate` of rg_handshake_init_batch_dev over
+ * init_desc and of rg_handshake_finish_batch_dev over resp_desc.
+ *
+ * The inert row is { offset 0, len 0, RG_KEY_SKIP }, with 24 zero bytes for an address row, and every row of every
+ * list beyond its count is the inert row, so a replayed graph never sees stale rows.  Every consumer turns it away on
+ * its length rule, which it applies before it reads buf (offset 0 is aligned and a frame of 0 bytes is inside any buf):
+ *   rg_cookie_reply_batch_dev, rg_rate_count_batch_dev  len is neither 148 nor 92: RG_PKT_INVALID / not counted
+ *   rg_handshake_init_batch_dev                         len is not 148: RG_PKT_INVALID
+ *   rg_handshake_finish_batch_dev                       len is not 92: RG_PKT_INVALID
+ *   rg_peer_cookie_consume_batch_dev                    len is not 64: RG_PKT_INVALID
+ *   rg_recv_batch_dev_resident                          W < 16: no header read, no lookup, RG_PKT_INVALID from the open
+ * A listed row carries key_idx 0: the chains only tell RG_KEY_SKIP from any other value.
+ *
+ * Per datagram the result of rg_demux_batch_dev equals this loop, bit for bit on every output byte:
+ *   rank = {hs: 0, ck: 0, data: 0}; seen = {hs: 0, ck: 0, data: 0}
+ *   for i in array order:
+ *     d = desc[i]; cls[i] = 0; pos[i] = RG_KEY_SKIP
+ *     d.key_idx == RG_KEY_SKIP                     -> RG_PKT_REJECTED, nothing read (an empty slot of the receive ring)
+ *     d.offset % 16 != 0                           -> RG_PKT_UNALIGNED                   (lib.rs:613)
+ *     d.len < 4, or d.offset + d.len > buf_len
+ *     (in 64 bits, without wrapping)               -> RG_PKT_INVALID                     (lib.rs:620)
+ *     t = the little-endian u32 at buf + d.offset
+ *     t == 1: len == 148 ? list hs   : RG_PKT_INVALID   (handshake.rs:45, mut_from_bytes is exact-size)
+ *     t == 2: len == 92  ? list hs   : RG_PKT_INVALID   (handshake.rs:149)
+ *     t == 3: len == 64  ? list ck   : RG_PKT_INVALID   (handshake.rs:238)
+ *     t == 4:              list data                    (the framing verdicts stay the receive's own)
+ *     else                                         -> RG_PKT_INVALID                     (lib.rs:628)
+ *     "list L": seen[L]++; k = rank[L]
+ *        k < cap[L] -> rank[L]++; row k of L's arrays = d (key_idx written as 0) and addrs[i];
+ *                      cls[i] = t; pos[i] = k; status[i] = RG_PKT_PENDING   (the verdict is the chain's)
+ *        else       -> cls[i] = t; status[i] = RG_PKT_FULL                  (dropped, like a full socket buffer)
+ *   counts[0..3) = rank, counts[3..6) = seen   (hs, ck, data)
+ * computed as one ordered compaction over the n datagrams whose sum carries the three counts: the count walk reads
+ * each datagram's type word once and leaves its class in cls, the rank walk reads cls and places the rows, and a pad
+ * pass over the lists' capacities writes the inert tails behind counts[0..3).  RG_PKT_PENDING is the honest verdict
+ * here: nothing has judged the message yet.
+ *
+ * rg_demux_verdict_batch_dev, one lane per datagram: for every i with status[i] == RG_PKT_PENDING,
+ *   cls[i] == 1 or 2 and pos[i] < cap_hs   -> f = hs_filter_status[pos[i]]; f != RG_PKT_OK ? f
+ *                                             : cls[i] == 1 ? init_status[pos[i]] : finish_status[pos[i]]
+ *   cls[i] == 3 and pos[i] < cap_ck        -> cookie_status[pos[i]]
+ *   cls[i] == 4 and pos[i] < cap_data      -> data_status[pos[i]]
+ * Any of the five chain status pointers may be NULL: its datagrams stay RG_PKT_PENDING.  A pos out of range or a cls
+ * outside 1-4 stays RG_PKT_PENDING and is never used as an index.  After this call status[n] is what a loop of
+ * recv_message over the batch returns, in the caller's order.
+ *
+ * Unlike the reference: (a) a descriptor with key_idx == RG_KEY_SKIP is an empty slot and reads RG_PKT_REJECTED, where
+ * the reference has no such thing as a datagram that did not arrive; (b) the lists have capacities, and a message past
+ * its list's capacity reads RG_PKT_FULL and is dropped, where the reference handles one message at a time and can
+ * never be full; (c) a type-4 datagram of any length is listed -- the reference's length and framing checks of a data
+ * packet (lib.rs:635-650) run in rg_recv_batch_dev_resident, whose verdict the way back returns. */
+typedef struct rg_demux_lists {      /* host struct, read at call time; every pointer is device memory */
+    rg_pkt_desc *hs_desc;            /* [cap_hs] types 1 and 2 in array order */
+    rg_src_addr *hs_addrs;           /* [cap_hs] */
+    rg_pkt_desc *init_desc;          /* [cap_hs] row k: hs_desc[k] if type 1, else inert */
+    rg_pkt_desc *resp_desc;          /* [cap_hs] row k: hs_desc[k] if type 2, else inert */
+    rg_pkt_desc *ck_desc;            /* [cap_ck] type 3 */
+    rg_pkt_desc *data_desc;          /* [cap_data] type 4 */
+    rg_src_addr *data_addrs;         /* [cap_data] */
+    uint32_t cap_hs, cap_ck, cap_data;
+} rg_demux_lists;
+
+size_t rg_demux_workspace_size(size_t n);
+int rg_demux_batch_dev(rg_ctx *ctx, const rg_pkt_desc *desc /* [n] */, const rg_src_addr *addrs /* [n] */, size_t n,
+                       const uint8_t *buf, size_t buf_len, const rg_demux_lists *lists /* host */,
+                       uint8_t *status /* [n] */, uint8_t *cls /* [n] */, uint32_t *pos /* [n] */,
+                       uint32_t *counts /* [6] */, void *workspace, size_t workspace_len, void *stream);
+int rg_demux_verdict_batch_dev(rg_ctx *ctx, const uint8_t *cls /* [n] */, const uint32_t *pos /* [n] */, size_t n,
+                               const uint8_t *hs_filter_status /* [cap_hs] or NULL */,
+                               const uint8_t *init_status /* [cap_hs] or NULL */,
+                               const uint8_t *finish_status /* [cap_hs] or NULL */, uint32_t cap_hs,
+                               const uint8_t *cookie_status /* [cap_ck] or NULL */, uint32_t cap_ck,
+                               const uint8_t *data_status /* [cap_data] or NULL */, uint32_t cap_data,
+                               uint8_t *status /* [n] */, void *stream);
 
 /* ------------------------------------------- several GPUs, one thread */
 /* The reference's host is one thread owning one Sessions (RefCell, rustyguard-core/src/lib.rs:

@@ -161,6 +161,11 @@ SIGNATURES = {
                                                   c_vp]),
     "rg_endpoint_gate_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_size, c_vp, c_vp, c_vp]),
     "rg_endpoint_peers_batch_dev": (c_int, [c_vp, c_vp, c_u32, c_vp, c_size, c_vp, c_vp, c_vp]),
+    "rg_demux_workspace_size": (c_size, [c_size]),
+    "rg_demux_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_size, c_vp, c_size, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_size,
+                                   c_vp]),
+    "rg_demux_verdict_batch_dev": (c_int, [c_vp, c_vp, c_vp, c_size, c_vp, c_vp, c_vp, c_u32, c_vp, c_u32, c_vp, c_u32,
+                                           c_vp, c_vp]),
 }
 
 # include/rg_aead_test.h: exported by the test library (librg_aead_test.so) only

@@ -29,7 +29,8 @@ LIB = os.path.join(LIBDIR, "librg_aead.so")
 TEST_LIB = os.path.join(LIBDIR, "librg_aead_test.so")
 KERNELS = ["rg_kernels.hip", "rg_tile.hip", "rg_pipe.hip", "rg_flat.hip", "rg_mac.hip", "rg_cookie.hip",
            "rg_replay.hip", "rg_send.hip", "rg_handshake.hip", "rg_route.hip", "rg_peerstate.hip",
-           "rg_session.hip", "rg_timers.hip", "rg_pending.hip", "rg_ratelimit.hip", "rg_endpoint.hip"]
+           "rg_session.hip", "rg_timers.hip", "rg_pending.hip", "rg_ratelimit.hip", "rg_endpoint.hip",
+           "rg_demux.hip"]
 HOST = ["rg_ctx.cpp", "rg_batch.cpp", "rg_hostpipe.cpp", "rg_message.cpp", "rg_sessions.cpp", "rg_debug.cpp"]
 SOURCES = KERNELS + HOST
 HEADERS = ["rg_device.h", "rg_internal.h", "rg_host.h", "rg_blake2s.h", "rg_grouped.h", "rg_x25519.h",

@@ -2,9 +2,9 @@
 // buffer and event owners, the context and the group, shared by the host units (rg_ctx.cpp, rg_batch.cpp,
 // rg_hostpipe.cpp, rg_message.cpp, rg_sessions.cpp, rg_debug.cpp) and by the entry points that live beside
 // their kernels (rg_cookie.hip, rg_replay.hip, rg_send.hip, rg_handshake.hip, rg_route.hip, rg_peerstate.hip,
-// rg_session.hip, rg_timers.hip, rg_pending.hip, rg_ratelimit.hip, rg_endpoint.hip).  Nothing here depends on RG_TEST_HOOKS: the test library's hooks
-// are read through the four functions under "test hooks" below, defined in rg_debug.cpp, and change no type's
-// layout.
+// rg_session.hip, rg_timers.hip, rg_pending.hip, rg_ratelimit.hip, rg_endpoint.hip, rg_demux.hip).  Nothing
+// here depends on RG_TEST_HOOKS: the test library's hooks are read through the four functions under "test
+// hooks" below, defined in rg_debug.cpp, and change no type's layout.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -74,6 +74,12 @@
          medians of seven with min-max; and by host wall clock the read-back and numpy last-per-peer a caller does
          today.  Also written to profiles/endpoint_bench.json
 
+  demux  the device-resident inbound demultiplexer at 64 Ki and 1 Mi datagrams on an IMIX-like mix and an
+         all-handshake flood: rg_demux_batch_dev, rg_demux_verdict_batch_dev and rg_timer_turn_dev over as many rows by
+         stream events, medians of seven with min-max; by host wall clock the read-back, numpy split and upload they
+         replace; and rg_handshake_init_batch_dev over a padded against a dense list.  Also written to
+         profiles/demux_bench.json
+
 Prints one JSON object.  Synthetic data (random messages: every MAC check does the full work and
 rejects, which costs the same as accepting).  Legs named on the command line run alone (default: all)."""
 import hashlib
@@ -1529,16 +1535,229 @@ def endpoint_leg(eng):
     return res
 
 
+def demux_leg(eng):
+    """The device-resident inbound demultiplexer at 64 Ki and 1 Mi datagrams, one 256-byte slot of buf each, on an
+    IMIX-like mix (1 % handshake, 0.1 % cookie, the rest data) and an all-handshake flood (initiations and responses
+    in turn): rg_demux_batch_dev with every list as long as the batch, the same with lists only as long as what
+    arrives (what the pad pass costs), rg_demux_verdict_batch_dev, rg_timer_turn_dev over a table of as many peers
+    (one compact of the same shape) by stream events, medians of seven with min-max; and by host wall clock what the
+    two calls replace: the type words gathered and read back, a numpy split and the upload of the three lists with
+    their addresses, alone and with a resident receive enqueued in front.  Then rg_handshake_init_batch_dev over a
+    flood's init_desc and rg_handshake_finish_batch_dev over its resp_desc (inert rows interleaved) against the same
+    calls on the dense lists.  Written to profiles/demux_bench.json."""
+    import time
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import handshake_cases as hc  # the Python model makes the valid initiations
+
+    from rustyguard_amd import demux, session, timers
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    rng = np.random.default_rng(83)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    words = lambda a: dev(np.asarray(a, np.uint32).view(np.int32))  # noqa: E731
+    SLOT = 256
+    LEN = {1: 148, 2: 92, 3: 64, 4: 96}
+
+    def measure(fn, clock="gpu", reset=None):
+        ev = []
+        for _ in range(8):  # the first is the warm-up
+            if reset:
+                reset()  # outside the timed window
+            torch.cuda.synchronize()
+            if clock == "gpu":
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                ev.append(a.elapsed_time(b))
+            else:
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ev.append((time.perf_counter() - t0) * 1e3)
+        ts = sorted(ev[1:])
+        return {"ms_median": round(ts[len(ts) // 2], 4), "ms_min": round(ts[0], 4), "ms_max": round(ts[-1], 4)}
+
+    def batch(n, mix):
+        i = np.arange(n)
+        if mix == "imix":
+            u = rng.random(n)
+            types = np.where(u < 0.005, 1, np.where(u < 0.01, 2, np.where(u < 0.011, 3, 4)))
+        else:
+            types = 1 + i % 2
+        desc = np.zeros(n, DESC_DTYPE)
+        desc["offset"] = i.astype(np.uint64) * SLOT
+        desc["len"] = np.array([0, 148, 92, 64, 96], np.uint32)[types]
+        buf = torch.zeros(n * SLOT, dtype=torch.uint8, device="cuda")
+        buf.view(torch.int32)[::SLOT // 4] = dev(types.astype(np.int32))
+        return types, desc, buf
+
+    # the receive that runs in front of the wall-clock pair: cfg2, 64 Ki x 1500 B on one session
+    w = workloads.build("cfg2")
+    nk = len(w.receivers)
+    b = DeviceBatch(eng, w)
+    b.fill()
+    b.seal()
+    sealed = b.buf.clone()
+    rx = dev(aead.rx_table(w.receivers, np.arange(nk, dtype=np.uint32)))
+    ws_r, win = eng.replay_workspace(w.n, nk), torch.zeros(nk * 33, dtype=torch.int64, device="cuda")
+
+    def recv():
+        eng.recv_batch_dev_resident(b.keys, rx, win, b.desc_open, b.buf, b.status, workspace=ws_r)
+
+    def restore_recv():
+        b.buf.copy_(sealed)
+        win.zero_()
+
+    out = {}
+    for n in (1 << 16, 1 << 20):
+        row = {}
+        addrs = rng.integers(0, 256, (n, 24), dtype=np.uint8)
+        d_addrs = dev(addrs)
+        T = session.SessionTables(eng, n, n)
+        T.slot_peer[:] = words(np.arange(n))
+        T.peer_slot[:] = words(np.arange(n))
+        tm = timers.timer_rows(eng, n)
+        ka, rk = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+        gate, counts = torch.zeros(n, dtype=torch.uint8, device="cuda"), torch.zeros(2, dtype=torch.int32, device="cuda")
+        d_now, ws_t = dev(np.array([10**12], np.int64)), timers.timer_workspace(eng, n, n)
+        row["timer_turn_same_rows"] = measure(lambda: timers.turn_dev(eng, T, tm, d_now, ka, rk, gate, counts, workspace=ws_t))
+        for mix in ("imix", "flood"):
+            types, desc, buf = batch(n, mix)
+            d_desc = dev(desc.view(np.uint8).reshape(-1, 16))
+            seen = [int(((types == 1) | (types == 2)).sum()), int((types == 3).sum()), int((types == 4).sum())]
+            res = {"seen": seen}
+            for label, caps in (("demux_caps_n", (n, n, n)), ("demux_caps_seen", tuple(seen))):
+                D = demux.Demux(eng, n, *caps)
+                res[label] = measure(lambda: D.batch_dev(d_desc, d_addrs, buf))
+                assert [int(x) for x in D.counts.cpu().numpy()] == seen + seen
+                assert int((D.status == aead.PKT_PENDING).sum()) == n
+            chain = [dev(rng.integers(0, 4, c, dtype=np.uint8)) for c in (seen[0], seen[0], seen[0], seen[1], seen[2])]
+            saved = D.status.clone()
+
+            def verdict():
+                D.verdict_batch_dev(n, *chain)
+
+            # the call finishes every pending status: give them back before each repetition, or the repetitions
+            # after the first would find nothing pending and leave at once
+            res["verdict"] = measure(verdict, reset=lambda: D.status.copy_(saved))
+            assert int((D.status == aead.PKT_PENDING).sum()) == 0
+            D.status.copy_(saved)
+            pinned = torch.empty(n, dtype=torch.int32).pin_memory()
+            at = dev((desc["offset"] // 4).astype(np.int64))
+
+            def caller_today():
+                pinned.copy_(buf.view(torch.int32)[at], non_blocking=True)  # the type words, gathered, to the host
+                torch.cuda.synchronize()
+                t = pinned.numpy()
+                hs, ck, da = np.nonzero((t == 1) | (t == 2))[0], np.nonzero(t == 3)[0], np.nonzero(t == 4)[0]
+                lists = [dev(desc[hs].view(np.uint8)), dev(addrs[hs]), dev(desc[ck].view(np.uint8)),
+                         dev(desc[da].view(np.uint8)), dev(addrs[da])]
+                return lists
+
+            res["caller_today_wall"] = measure(caller_today, clock="wall")
+            res["demux_wall"] = measure(lambda: D.batch_dev(d_desc, d_addrs, buf), clock="wall")
+            # the same two with a resident receive of 64 Ki x 1500 B enqueued in front, as in a running loop: the
+            # host path's synchronise waits for it, the demux queues behind it
+            res["recv_then_caller_today_wall"] = measure(lambda: (recv(), caller_today()), clock="wall", reset=restore_recv)
+            res["recv_then_demux_wall"] = measure(lambda: (recv(), D.batch_dev(d_desc, d_addrs, buf)), clock="wall",
+                                                  reset=restore_recv)
+            row[mix] = res
+        out[f"datagrams_{n}"] = row
+        del T, tm
+
+    # init and finish over the padded lists against dense ones: 64 Ki datagrams, valid initiations and valid responses
+    # in turn.  The responses answer 32 Ki pending handshakes of a second key pair S to a peer P, made here by the calls
+    # the two sides would run.
+    n = 1 << 16
+    m = n // 2
+    rb = lambda k: bytes(rng.integers(0, 256, k, dtype=np.uint8))  # noqa: E731
+    sk_s, sk_p, psk = rb(32), rb(32), rb(32)
+    pk_s, pk_p = hc.pubkey(sk_s), hc.pubkey(sk_p)
+    own_s, own_p = dev(np.frombuffer(sk_s + pk_s, np.uint8)), dev(np.frombuffer(sk_p + pk_p, np.uint8))
+    peers_i = dev(hc.peer_rows([(pk_p, psk, hc.mac1_key(pk_p))] * 8))
+    rows_p = hc.peer_rows([(pk_s, psk, hc.mac1_key(pk_s))])
+    sids = np.arange(m, dtype=np.uint32) + 0x0100_0000
+    ts = dev(np.frombuffer(b"".join(hc.tai64n(1_900_000_000, i) for i in range(m)), np.uint8).reshape(m, 12))
+    msgs, pending = (torch.zeros((m, w_), dtype=torch.uint8, device="cuda") for w_ in (160, 128))
+    st_h = [torch.zeros(m, dtype=torch.uint8, device="cuda") for _ in range(3)]
+    eng.handshake_initiate_dev(own_s, peers_i, words(np.arange(m) % 8), None, dev(rng.integers(0, 256, (m, 32), dtype=np.uint8)),
+                               ts, dev(sids), None, None, msgs, pending, st_h[0])
+    desc_m = np.zeros(m, DESC_DTYPE)
+    desc_m["offset"], desc_m["len"] = np.arange(m, dtype=np.uint64) * 160, 148
+    res_p, responses, keys_p = (torch.zeros((m, w_), dtype=torch.uint8, device="cuda") for w_ in (128, 96, 64))
+    eng.handshake_init_dev(own_p, dev(rows_p), dev(aead.peer_table(rows_p)), dev(desc_m.view(np.uint8).reshape(-1, 16)), None,
+                           msgs, res_p, st_h[1])
+    eng.handshake_resp_dev(dev(rows_p), res_p, st_h[1], dev(rng.integers(0, 256, (m, 32), dtype=np.uint8)),
+                           words(np.arange(m) + 0x0200_0000), None, None, responses, keys_p, st_h[2])
+    torch.cuda.synchronize()
+    assert all((s_ == aead.PKT_OK).all().item() for s_ in st_h)
+    r = hc.Responder(41, npeers=8, neph=256)
+    base = np.zeros((256, SLOT), np.uint8)
+    for i in range(256):
+        msg, _ = hc.make_initiation(r.sk_i[i % 8], r.pk_r, r.esk_i[i], hc.tai64n(1_800_000_000, i), i)
+        base[i, :148] = np.frombuffer(msg, np.uint8)
+    frames = np.tile(base, (n // 256, 1))
+    frames[1::2] = 0
+    frames[1::2, :92] = responses.cpu().numpy()[:, :92]
+    buf = dev(frames.reshape(-1))
+    desc = np.zeros(n, DESC_DTYPE)
+    desc["offset"] = np.arange(n, dtype=np.uint64) * SLOT
+    desc["len"] = np.where(np.arange(n) % 2 == 0, 148, 92)
+    D = demux.Demux(eng, n, n, 0, 0)
+    D.batch_dev(dev(desc.view(np.uint8).reshape(-1, 16)), dev(rng.integers(0, 256, (n, 24), dtype=np.uint8)), buf)
+    peers = hc.peer_rows(r.peers)
+    d_own, d_peers, d_table = dev(r.own), dev(peers), dev(aead.peer_table(peers))
+    dense = dev(np.ascontiguousarray(desc[0::2]).view(np.uint8).reshape(-1, 16))
+    results, st = torch.zeros((n, 128), dtype=torch.uint8, device="cuda"), torch.zeros(n, dtype=torch.uint8, device="cuda")
+    padded_ms = measure(lambda: eng.handshake_init_dev(d_own, d_peers, d_table, D.init_desc, None, buf, results, st))
+    assert int((st == aead.PKT_OK).sum()) == n // 2 and int((st == aead.PKT_INVALID).sum()) == n // 2
+    dense_ms = measure(lambda: eng.handshake_init_dev(d_own, d_peers, d_table, dense, None, buf, results[:n // 2], st[:n // 2]))
+    assert (st[:n // 2] == aead.PKT_OK).all().item()
+    out["init_over_padded_list"] = {"rows": n, "initiations": n // 2, "padded": padded_ms, "dense": dense_ms}
+    pend_table, saved_pending = dev(aead.pending_table(sids)), pending.clone()
+    tk = torch.zeros((n, 64), dtype=torch.uint8, device="cuda")
+    pi, ro = (torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(2))
+    claim = torch.zeros(m, dtype=torch.int32, device="cuda")
+    dense_r = dev(np.ascontiguousarray(desc[1::2]).view(np.uint8).reshape(-1, 16))
+    give_back = lambda: pending.copy_(saved_pending)  # noqa: E731  (a finished row is wiped)
+    padded_ms = measure(lambda: eng.handshake_finish_dev(own_s, peers_i, pend_table, pending, D.resp_desc, None, buf, tk, pi, ro,
+                                                         claim, st), reset=give_back)
+    assert int((st == aead.PKT_OK).sum()) == m and int((st == aead.PKT_INVALID).sum()) == m
+    dense_ms = measure(lambda: eng.handshake_finish_dev(own_s, peers_i, pend_table, pending, dense_r, None, buf, tk[:m], pi[:m],
+                                                        ro[:m], claim, st[:m]), reset=give_back)
+    assert (st[:m] == aead.PKT_OK).all().item()
+    out["finish_over_padded_list"] = {"rows": n, "responses": m, "padded": padded_ms, "dense": dense_ms}
+    out["note"] = ("stream events around one call each, medians of 7 repetitions after one warm-up; one 256-byte slot of "
+                   "buf per datagram, so the type-word gather touches one line per datagram; caps_n = every list n rows "
+                   "(the pad pass writes what the mix leaves empty), caps_seen = every list exactly as long as what "
+                   "arrives; verdict with all five chain arrays, the pending statuses given back before every repetition; timer_turn_same_rows = rg_timer_turn_dev over n peers "
+                   "of one row each, nothing due; *_wall = host wall clock around the call and a device sync; "
+                   "caller_today = type words gathered on the device, copied to pinned memory, a synchronise, a numpy "
+                   "split and five uploads; recv_then_* = the same pair with rg_recv_batch_dev_resident over 64 Ki x "
+                   "1500 B of one session enqueued first inside the timed region (frames and window restored outside it); "
+                   "init_over_padded_list / finish_over_padded_list = rg_handshake_init_batch_dev over init_desc and "
+                   "rg_handshake_finish_batch_dev over resp_desc of a flood of valid initiations and valid responses in "
+                   "turn (half the rows of each inert) against the same calls over the dense lists, the pending rows given "
+                   "back before every repetition")
+    with open(os.path.join(root, "profiles", "demux_bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     legs = sys.argv[1:] or ["mac1", "cookie", "rx", "sessions", "replay", "send", "route", "handshake", "initiator",
-                            "peerstate", "session", "timers", "pending", "ratelimit", "endpoint"]
+                            "peerstate", "session", "timers", "pending", "ratelimit", "endpoint", "demux"]
     eng = aead.Engine(0)
     out = {}
     for name, leg in (("mac1", mac1_leg), ("cookie", cookie_leg), ("rx", rx_leg), ("sessions", sessions_leg),
                       ("replay", replay_leg), ("send", send_leg), ("route", route_leg), ("handshake", handshake_leg),
                       ("initiator", initiator_leg), ("peerstate", peerstate_leg), ("session", session_leg),
                       ("timers", timers_leg), ("pending", pending_leg), ("ratelimit", ratelimit_leg),
-                      ("endpoint", endpoint_leg)):
+                      ("endpoint", endpoint_leg), ("demux", demux_leg)):
         if name in legs:
             out[name] = leg(eng)
     print(json.dumps(out))
