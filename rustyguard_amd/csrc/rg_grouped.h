@@ -1,18 +1,26 @@
 // rg_grouped.h -- what a batch pass over packets grouped by a row shares: the device anti-replay commit
-// (rg_replay.hip: row = window, a segmented prefix maximum), the device send-counter reservation
-// (rg_send.hip: row = session, a segmented count) and the peers' timestamp check (rg_peerstate.hip: row =
-// peer, a segmented prefix maximum).  Device code and its launchers only.
+// (rg_replay.hip: row = window, a segmented prefix maximum), the peers' timestamp check (rg_peerstate.hip:
+// row = peer, a segmented prefix maximum), the handshake rate limiter (rg_ratelimit.hip: row = sketch bucket,
+// a segmented count) and the device send-counter reservation (rg_send.hip: row = session, a segmented
+// count).  Device code and its launchers only.
 //   Grouped          the device view of a batch and its grouped order; also the key of the radix passes
 //   SegPair          the segmented-scan monoid over a value type and an operation; Tally the plain sum
+//   AggLayout        the tiles' aggregates in a workspace, Agg their typed pointers
 //   block_prefix     exclusive scan of one SegPair per lane over a workgroup, carry_kernel over the tiles'
 //                    aggregates
-//   AggLayout        the tiles' aggregates in a workspace, Agg their typed pointers
 //   compact          the ordered compaction of an array: count, carry, rank.  Its users say what an item
 //                    contributes and what a ranked item does: the eligible handshakes and the free rows of
-//                    the session install (rg_session.hip), the two lists of the timer turn (rg_timers.hip)
+//                    the session install (rg_session.hip), the two lists of the timer turn (rg_timers.hip),
+//                    of the pending turn (rg_pending.hip), the three of the inbound demux (rg_demux.hip)
 //   GroupLayout      the workspace arrays every grouped pass has, group_rows their typed pointers and the order
-// How a tile of kGroupTile grouped packets is walked is each segmented file's own: the walk follows the
-// monoid.  The plain sum has one walk, compact's.
+//   segscan          the segmented scan over the grouped order: reduce, carry, verdict.  Its users say what an
+//                    item loads and contributes, how it is judged with the prefix of its row and what the
+//                    row's last item hands on: the first three files above
+// Both cores walk a tile of kGroupTile positions the same way, kTileItems consecutive positions a lane and
+// the lanes' runs scanned through LDS, which serves any monoid.  rg_send.hip shares everything here but
+// that walk: its value is a count of flags, so a wave ranks 64 positions a round by ballots and popcounts
+// with one meeting in LDS per tile where block_prefix takes eight steps (with its measured
+// times).
 //
 // The grouping is stable, by the passes of an LSD radix sort over the 32-bit key, 8 bits per pass.  KeyOf is
 // a small struct passed by value with `__device__ uint32_t operator()(uint32_t i) const`: the grouping key
@@ -28,7 +36,7 @@
 namespace rg {
 
 constexpr uint32_t kGroupTile = 2048; // packets per workgroup of 256 lanes, in the scans and the radix passes
-constexpr uint32_t kRadixItems = kGroupTile / 256;
+constexpr uint32_t kTileItems = kGroupTile / 256; // positions per lane of a tile
 
 // A batch of n packets, each with a row word (rows[i]; RG_KEY_SKIP or >= nrows: no row), and the packet
 // indices grouped by row.  A packet without a row rides along in row 0's group.
@@ -73,6 +81,40 @@ __device__ __forceinline__ SegPair<V, Op> join(const SegPair<V, Op> &a, const Se
     return SegPair<V, Op>{a.f | b.f, b.f ? b.v : Op{}(a.v, b.v)};
 }
 
+// The per-tile aggregates of a scan over n items, in this order in the caller's workspace.
+struct AggLayout {
+    uint64_t agg_val;  // [nblk] V and
+    uint64_t agg_flag; // [nblk] u32
+    uint32_t nblk;     // tiles of kGroupTile items
+    void take_agg(WorkspaceCursor &ws, uint64_t n, uint64_t value_size) {
+        nblk = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
+        agg_val = ws.take((uint64_t)nblk * value_size);
+        agg_flag = ws.take((uint64_t)nblk * 4);
+    }
+};
+template <class V>
+struct Agg {
+    V *val;
+    uint32_t *flag;
+    uint32_t nblk;
+    Agg() = default;
+    Agg(uint8_t *ws, const AggLayout &L)
+        : val(reinterpret_cast<V *>(ws + L.agg_val)), flag(reinterpret_cast<uint32_t *>(ws + L.agg_flag)),
+          nblk(L.nblk) {}
+};
+// the workgroup's tile: lane 0 stores its aggregate; what the tile starts from, once carry_kernel has run
+template <class Pair>
+__device__ __forceinline__ void store_tile(const Agg<typename Pair::value_type> &agg, const Pair &total) {
+    if (threadIdx.x == 0) {
+        agg.flag[blockIdx.x] = total.f;
+        agg.val[blockIdx.x] = total.v;
+    }
+}
+template <class Pair>
+__device__ __forceinline__ Pair tile_start(const Agg<typename Pair::value_type> &agg) {
+    return Pair{agg.flag[blockIdx.x], agg.val[blockIdx.x]};
+}
+
 // exclusive prefix of one Pair per lane over the workgroup's 256 lanes (returned), and their total
 template <class Pair>
 __device__ __forceinline__ Pair block_prefix(const Pair &mine, Pair &total) {
@@ -102,18 +144,17 @@ __device__ __forceinline__ Pair block_prefix(const Pair &mine, Pair &total) {
 
 // the tiles' aggregates -> what each tile starts from (exclusive), in place; one workgroup
 template <class Pair>
-__global__ __launch_bounds__(256) void carry_kernel(uint32_t *agg_flag, typename Pair::value_type *agg_val,
-                                                    uint32_t nblk) {
-    const uint32_t t = threadIdx.x;
+__global__ __launch_bounds__(256) void carry_kernel(Agg<typename Pair::value_type> agg) {
+    const uint32_t t = threadIdx.x, nblk = agg.nblk;
     const uint32_t per = (nblk + 255) / 256, lo = min(t * per, nblk), hi = min(lo + per, nblk);
     Pair run{0u, 0u};
-    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{agg_flag[j], agg_val[j]});
+    for (uint32_t j = lo; j < hi; ++j) run = join(run, Pair{agg.flag[j], agg.val[j]});
     Pair total;
     Pair ex = block_prefix(run, total);
     for (uint32_t j = lo; j < hi; ++j) {
-        const Pair cur{agg_flag[j], agg_val[j]};
-        agg_flag[j] = ex.f;
-        agg_val[j] = ex.v;
+        const Pair cur{agg.flag[j], agg.val[j]};
+        agg.flag[j] = ex.f;
+        agg.val[j] = ex.v;
         ex = join(ex, cur);
     }
 }
@@ -126,29 +167,6 @@ struct Plus {
 };
 template <class V>
 using Tally = SegPair<V, Plus<V>>;
-
-constexpr uint32_t kTileItems = kGroupTile / 256; // positions per lane of a tile, consecutive
-
-// The per-tile aggregates of a scan over n items, in this order in the caller's workspace.
-struct AggLayout {
-    uint64_t agg_val;  // [nblk] V and
-    uint64_t agg_flag; // [nblk] u32
-    uint32_t nblk;     // tiles of kGroupTile items
-    void take_agg(WorkspaceCursor &ws, uint64_t n, uint64_t value_size) {
-        nblk = (uint32_t)((n + kGroupTile - 1) / kGroupTile);
-        agg_val = ws.take((uint64_t)nblk * value_size);
-        agg_flag = ws.take((uint64_t)nblk * 4);
-    }
-};
-template <class V>
-struct Agg {
-    V *val;
-    uint32_t *flag;
-    uint32_t nblk;
-    Agg(uint8_t *ws, const AggLayout &L)
-        : val(reinterpret_cast<V *>(ws + L.agg_val)), flag(reinterpret_cast<uint32_t *>(ws + L.agg_flag)),
-          nblk(L.nblk) {}
-};
 
 // A pass is a small struct passed by value.  Both walks call `V item(uint64_t pos) const` for every pos < n:
 // what the position contributes to the sum (several counts may share a V, each in bits of its own).  The
@@ -192,7 +210,7 @@ template <class V, class CountPass, class RankPass>
 inline void compact(CountPass count, RankPass rank, uint32_t n, const Agg<V> &agg, hipStream_t st) {
     const dim3 tiles(agg.nblk), wg(256);
     hipLaunchKernelGGL((compact_count_kernel<V, CountPass>), tiles, wg, 0, st, count, n, agg);
-    hipLaunchKernelGGL(carry_kernel<Tally<V>>, dim3(1), wg, 0, st, agg.flag, agg.val, agg.nblk);
+    hipLaunchKernelGGL(carry_kernel<Tally<V>>, dim3(1), wg, 0, st, agg);
     hipLaunchKernelGGL((compact_rank_kernel<V, RankPass>), tiles, wg, 0, st, rank, n, agg);
 }
 
@@ -212,7 +230,7 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(KeyOf key, uint32_t n, 
     s_h[threadIdx.x] = 0;
     __syncthreads();
     const uint64_t base = (uint64_t)blockIdx.x * kGroupTile;
-    for (uint32_t k = 0; k < kRadixItems; ++k) {
+    for (uint32_t k = 0; k < kTileItems; ++k) {
         const uint64_t pos = base + k * 256 + threadIdx.x;
         if (pos < n) atomicAdd(&s_h[(key(src ? src[pos] : (uint32_t)pos) >> shift) & 255u], 1u);
     }
@@ -258,10 +276,9 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(KeyOf key, uint32_t 
     for (uint32_t q = 0; q < 4; ++q) s_off[q][t] = 0;
     __syncthreads();
     const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
-    constexpr uint32_t kRounds = kGroupTile / 256;
-    uint32_t idx[kRounds], dg[kRounds];
+    uint32_t idx[kTileItems], dg[kTileItems];
 #pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
+    for (uint32_t r = 0; r < kTileItems; ++r) {
         const uint64_t pos = base + r * 64 + lane;
         const bool ok = pos < n;
         idx[r] = ok ? (src ? src[pos] : (uint32_t)pos) : 0u;
@@ -279,7 +296,7 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(KeyOf key, uint32_t 
     }
     __syncthreads();
 #pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
+    for (uint32_t r = 0; r < kTileItems; ++r) {
         const bool ok = dg[r] < 256u;
         uint64_t same = __ballot(ok);
 #pragma unroll
@@ -332,12 +349,10 @@ struct GroupLayout : AggLayout {
     }
 };
 
-// What the scan kernels of a grouped pass take: the view, the aggregates, the tile count.
+// What the scan kernels of a grouped pass take: the view and the tiles' aggregates.
 template <class V>
 struct GroupScan : Grouped {
-    V *agg_val;
-    uint32_t *agg_flag;
-    uint32_t nblk;
+    Agg<V> agg;
 };
 // Groups the batch by row on `st` and returns the scan's arguments, out of the workspace at ws.
 template <class V>
@@ -347,8 +362,99 @@ inline GroupScan<V> group_rows(const uint32_t *rows, uint32_t nrows, uint32_t n,
     g.order = group_by_key(g, n, L.nblk, L.passes, reinterpret_cast<uint32_t *>(ws + L.hist),
                            reinterpret_cast<uint32_t *>(ws + L.order[0]),
                            reinterpret_cast<uint32_t *>(ws + L.order[1]), st);
-    return GroupScan<V>{g, reinterpret_cast<V *>(ws + L.agg_val), reinterpret_cast<uint32_t *>(ws + L.agg_flag),
-                        L.nblk};
+    return GroupScan<V>{g, Agg<V>(ws, L)};
+}
+
+// ------------------------------------------------------ segmented scan
+// One grouped packet as the scan sees it; a pass's Item derives from it.
+struct SegItem {
+    uint32_t i, key; // the packet; its row, 0 for a packet that rides along
+    bool head, row;  // the first of its key in the grouped order; it has a row
+};
+
+// A pass is a small struct passed by value, all of its hooks const and __forceinline__ (the verdict walk keeps a
+// lane's kTileItems items in registers):
+//   Pair, Item, g     its SegPair, its item and the GroupScan that group_rows returned
+//   void load(Item &)                  the item's own fields, once the core has filled SegItem's
+//   V value(const Item &)              what the item contributes; V(0) is the identity
+//   void seen(const Item &)            the reduce walk only, once per item
+//   void judge(const Item &, V before, V upto)   the verdict walk: Op over the values of the item's row ahead
+//                                      of it (the identity at the row's head), and up to and with it
+//   void tail(uint64_t pos, const Item &, V upto)   behind judge, at the last grouped position of a row
+template <class Pass>
+__device__ __forceinline__ typename Pass::Item seg_load(const Pass &p, uint64_t pos, uint32_t prev_key) {
+    typename Pass::Item it{};
+    it.i = p.g.index_at(pos);
+    const uint32_t w = p.g.rows[it.i];
+    it.row = p.g.has_row(w);
+    it.key = it.row ? w : 0u;
+    it.head = pos == 0 || it.key != prev_key;
+    p.load(it);
+    return it;
+}
+template <class Pass>
+__device__ __forceinline__ typename Pass::Pair seg_pair(const Pass &p, const typename Pass::Item &it) {
+    return typename Pass::Pair{it.head ? 1u : 0u, p.value(it)};
+}
+
+template <class Pass>
+__global__ __launch_bounds__(256) void seg_reduce_kernel(Pass p) {
+    using Pair = typename Pass::Pair;
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kTileItems;
+    uint32_t prev = p.g.key_before(base);
+    Pair run{0u, 0u};
+    for (uint32_t k = 0; k < kTileItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos >= p.g.n) break;
+        const typename Pass::Item it = seg_load(p, pos, prev);
+        prev = it.key;
+        p.seen(it);
+        run = join(run, seg_pair(p, it));
+    }
+    Pair total;
+    (void)block_prefix(run, total);
+    store_tile(p.g.agg, total);
+}
+
+template <class Pass>
+__global__ __launch_bounds__(256) void seg_verdict_kernel(Pass p) {
+    using Pair = typename Pass::Pair;
+    using V = typename Pair::value_type;
+    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kTileItems;
+    uint32_t prev = p.g.key_before(base);
+    typename Pass::Item items[kTileItems];
+    Pair run{0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < kTileItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos < p.g.n) {
+            items[k] = seg_load(p, pos, prev);
+            prev = items[k].key;
+            run = join(run, seg_pair(p, items[k]));
+        } else items[k] = typename Pass::Item{};
+    }
+    Pair total;
+    const Pair mine = block_prefix(run, total);
+    Pair ex = join(tile_start<Pair>(p.g.agg), mine);
+#pragma unroll
+    for (uint32_t k = 0; k < kTileItems; ++k) {
+        const uint64_t pos = base + k;
+        if (pos >= p.g.n) break;
+        const typename Pass::Item &it = items[k];
+        const V before = it.head ? V(0) : ex.v;
+        ex = join(ex, seg_pair(p, it));
+        p.judge(it, before, ex.v);
+        if (p.g.is_tail(pos, it.key)) p.tail(pos, it, ex.v);
+    }
+}
+
+// reduce -> carry -> verdict over the grouped batch p.g on st
+template <class Pass>
+inline void segscan(const Pass &p, hipStream_t st) {
+    const dim3 tiles(p.g.agg.nblk), wg(256);
+    hipLaunchKernelGGL(seg_reduce_kernel<Pass>, tiles, wg, 0, st, p);
+    hipLaunchKernelGGL(carry_kernel<typename Pass::Pair>, dim3(1), wg, 0, st, p.g.agg);
+    hipLaunchKernelGGL(seg_verdict_kernel<Pass>, tiles, wg, 0, st, p);
 }
 
 } // namespace rg

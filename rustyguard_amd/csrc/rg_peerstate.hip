@@ -17,9 +17,10 @@
 // max(latest, the group's maximum) behind.  Kernels of that call, all on its stream:
 //   ts_prep      rows[i] = the peer of an eligible row (status OK, peer < npeers), RG_KEY_SKIP otherwise; every
 //                other row gets its final answer here (an OK row without a peer row: RG_PKT_INVALID, wiped)
-//   radix_hist / radix_scan / radix_scatter, carry   rg_grouped.h: the stable grouping by peer, the tiles' carries
-//   ts_reduce    per workgroup of 2048 grouped rows the aggregate of the segmented prefix maximum
-//   ts_verdict   every eligible row's prefix maximum and verdict; the running maximum at each peer's last row
+//   radix_hist / radix_scan / radix_scatter   rg_grouped.h: the stable grouping by peer
+//   seg_reduce / carry / seg_verdict   rg_grouped.h's segscan with TsArgs as its pass: per workgroup of 2048 grouped
+//                rows the aggregate of the segmented prefix maximum, the tiles' carries, then every eligible row's
+//                prefix maximum and verdict (judge) and the running maximum at each peer's last row (tail)
 //   ts_advance   one lane per peer with traffic: latest_ts
 // The value is the 96-bit timestamp as an integer, big-endian as TAI64N orders it, in an unsigned __int128; zero
 // is the identity (a zeroed row is Peer::new, and no timestamp is below it).  A row without a peer rides along
@@ -41,14 +42,12 @@ namespace {
 
 // rg_hs_peer_state as 4 uint4: (latest_ts[0..12], has_cookie), cookie, last_sent_mac1, pad
 constexpr uint32_t kStateQuads = 4;
-constexpr uint32_t kItems = kGroupTile / 256; // grouped rows per lane, consecutive
 
 // ------------------------------------------------------------- timestamps
 using Ts = unsigned __int128; // be64(ts[0..8]) << 32 | be32(ts[8..12])
 struct TsMax {
     __device__ __forceinline__ Ts operator()(Ts a, Ts b) const { return a > b ? a : b; }
 };
-using Pair = SegPair<Ts, TsMax>;
 
 // the 12 bytes as they lie in memory (three little-endian words) -> their big-endian value, and back
 __device__ __forceinline__ Ts ts_value(uint32_t w0, uint32_t w1, uint32_t w2) {
@@ -73,7 +72,18 @@ TsLayout ts_layout(uint64_t n, uint32_t npeers) {
     return L;
 }
 
+// as the init call leaves the row of a message that failed: zeros, peer = RG_PEER_NONE
+__device__ __forceinline__ void wipe_result(uint4 *row) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) row[q] = q == 6 ? make_uint4(0, 0, 0, RG_PEER_NONE) : make_uint4(0, 0, 0, 0);
+}
+
+// The call's arguments; the scan kernels take them as the pass of rg_grouped.h's segscan.
 struct TsArgs {
+    using Pair = SegPair<Ts, TsMax>;
+    struct Item : SegItem {
+        Ts ts; // 0 for a row that rides along
+    };
     uint4 *state;        // [npeers] rg_hs_peer_state
     uint4 *results;      // [n] rg_hs_init_result rows of 8 uint4; word 3 of quad 6 is the peer
     uint8_t *status;     // [n]
@@ -83,13 +93,29 @@ struct TsArgs {
     uint32_t npeers;
     uint32_t n;
     GroupScan<Ts> g; // g.rows = rows
-};
 
-// as the init call leaves the row of a message that failed: zeros, peer = RG_PEER_NONE
-__device__ __forceinline__ void wipe_result(uint4 *row) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) row[q] = q == 6 ? make_uint4(0, 0, 0, RG_PEER_NONE) : make_uint4(0, 0, 0, 0);
-}
+    __device__ __forceinline__ void load(Item &it) const {
+        if (it.row) {
+            const uint4 q = results[8ull * it.i + 6];
+            it.ts = ts_value(q.x, q.y, q.z);
+        }
+    }
+    __device__ __forceinline__ Ts value(const Item &it) const { return it.ts; }
+    __device__ __forceinline__ void seen(const Item &) const {}
+    // before = the peer's largest eligible timestamp ahead of this row
+    __device__ __forceinline__ void judge(const Item &it, Ts before, Ts) const {
+        if (!it.row) return;
+        const uint4 s0 = state[(uint64_t)kStateQuads * it.key]; // read only here; ts_advance writes it
+        const Ts latest = ts_value(s0.x, s0.y, s0.z);
+        if (it.ts < (before > latest ? before : latest)) { // equal passes: the reference compares with <
+            wipe_result(results + 8ull * it.i);
+            peers_out[it.i] = RG_PEER_NONE;
+            status[it.i] = RG_PKT_REJECTED; // after the row
+        } else peers_out[it.i] = it.key;
+    }
+    // the peer's last row of the batch hands the running maximum to ts_advance
+    __device__ __forceinline__ void tail(uint64_t pos, const Item &, Ts upto) const { lf[pos] = upto; }
+};
 
 __global__ __launch_bounds__(256) void ts_prep_kernel(TsArgs a) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -97,7 +123,7 @@ __global__ __launch_bounds__(256) void ts_prep_kernel(TsArgs a) {
     uint32_t row = RG_KEY_SKIP;
     if (a.status[i] == RG_PKT_OK) {
         const uint32_t peer = a.results[8ull * i + 6].w;
-        if (peer < a.npeers) row = peer; // eligible: the verdict kernel answers
+        if (peer < a.npeers) row = peer; // eligible: the scan's judge answers
         else {
             wipe_result(a.results + 8ull * i);
             a.peers_out[i] = RG_PEER_NONE;
@@ -105,84 +131,6 @@ __global__ __launch_bounds__(256) void ts_prep_kernel(TsArgs a) {
         }
     } else a.peers_out[i] = RG_PEER_NONE; // keeps its status
     a.rows[i] = row;
-}
-
-// one grouped row as the scan sees it
-struct Item {
-    uint32_t i, key;
-    Ts ts; // 0 for a row that rides along
-    bool head, elig;
-};
-__device__ __forceinline__ Item load_item(const TsArgs &a, uint64_t pos, uint32_t prev_key) {
-    Item it{};
-    it.i = a.g.index_at(pos);
-    const uint32_t w = a.g.rows[it.i];
-    it.elig = a.g.has_row(w);
-    it.key = it.elig ? w : 0u;
-    if (it.elig) {
-        const uint4 q = a.results[8ull * it.i + 6];
-        it.ts = ts_value(q.x, q.y, q.z);
-    }
-    it.head = pos == 0 || it.key != prev_key;
-    return it;
-}
-__device__ __forceinline__ Pair pair_of(const Item &it) { return Pair{it.head ? 1u : 0u, it.ts}; }
-
-__global__ __launch_bounds__(256) void ts_reduce_kernel(TsArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Pair run{0u, Ts(0)};
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item it = load_item(a, pos, prev);
-        prev = it.key;
-        run = join(run, pair_of(it));
-    }
-    Pair total;
-    (void)block_prefix(run, total);
-    if (threadIdx.x == 0) {
-        a.g.agg_flag[blockIdx.x] = total.f;
-        a.g.agg_val[blockIdx.x] = total.v;
-    }
-}
-
-__global__ __launch_bounds__(256) void ts_verdict_kernel(TsArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Item items[kItems];
-    Pair run{0u, Ts(0)};
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos < a.g.n) {
-            items[k] = load_item(a, pos, prev);
-            prev = items[k].key;
-            run = join(run, pair_of(items[k]));
-        } else items[k] = Item{};
-    }
-    Pair total;
-    const Pair mine = block_prefix(run, total);
-    Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, mine);
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item &it = items[k];
-        const Ts before = it.head ? Ts(0) : ex.v; // the peer's largest eligible timestamp ahead of this row
-        ex = join(ex, pair_of(it));
-        if (it.elig) {
-            const uint4 s0 = a.state[(uint64_t)kStateQuads * it.key]; // read only here; ts_advance writes it
-            const Ts latest = ts_value(s0.x, s0.y, s0.z);
-            if (it.ts < (before > latest ? before : latest)) { // equal passes: the reference compares with <
-                wipe_result(a.results + 8ull * it.i);
-                a.peers_out[it.i] = RG_PEER_NONE;
-                a.status[it.i] = RG_PKT_REJECTED; // after the row
-            } else a.peers_out[it.i] = it.key;
-        }
-        // the peer's last row of the batch hands the running maximum to ts_advance
-        if (a.g.is_tail(pos, it.key)) a.lf[pos] = ex.v;
-    }
 }
 
 // One lane per peer with traffic (the lane of its last grouped row): latest_ts = max(latest_ts, the group's
@@ -357,10 +305,7 @@ extern "C" int rg_peer_ts_batch_dev(rg_ctx *ctx, rg_hs_peer_state *state, uint32
     RG_HIP(hipGetLastError(), "peer ts: prep launch");
     if (npeers == 0) return RG_OK; // no row is eligible: prep answered them all
     a.g = rg::group_rows<rg::Ts>(a.rows, npeers, a.n, ws, L.g, st);
-    const dim3 tiles(L.g.nblk);
-    hipLaunchKernelGGL(rg::ts_reduce_kernel, tiles, kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::carry_kernel<rg::Pair>, dim3(1), kWg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
-    hipLaunchKernelGGL(rg::ts_verdict_kernel, tiles, kWg, 0, st, a);
+    rg::segscan(a, st);
     hipLaunchKernelGGL(rg::ts_advance_kernel, lanes(n), kWg, 0, st, a);
     RG_HIP(hipGetLastError(), "peer ts: scan launch");
     return RG_OK;

@@ -18,12 +18,12 @@
 //                 address, then the bucket word of each of its items, RG_KEY_SKIP for a message that is not counted
 //   radix_hist / radix_scan / radix_scatter   rg_grouped.h: the items grouped by bucket; none for a sketch of one
 //                 bucket
-//   rate_reduce   per tile of 2048 grouped items the aggregate of the segmented count
-//   carry         rg_grouped.h: one workgroup scans the aggregates
-//   rate_verdict  every counted item's estimate; the count of its bucket at the bucket's last item
+//   seg_reduce / carry / seg_verdict   rg_grouped.h's segscan with CountArgs as its pass: per tile of 2048 grouped
+//                 items the aggregate of the segmented count, one workgroup scans the aggregates, then every counted
+//                 item's estimate (judge) and the count of its bucket at the bucket's last item (tail)
 //   rate_finish   one lane per item: the lane of a bucket's last item stores the bucket; one lane per message: the
 //                 minimum over its items, counts_out, then overload_out
-// An item that is not counted rides along in bucket 0's group and adds nothing.  Buckets are read by rate_verdict
+// An item that is not counted rides along in bucket 0's group and adds nothing.  Buckets are read by the scan's judge
 // and written by rate_finish, never both in one kernel.  Plain vector stores only; no atomics on global memory.
 // The turn's kernels: rate_decide, one lane, reads the clock and writes reset_out and last_reset_ns; rate_wipe
 // behind it reads reset_out alone, so the decision is taken once and a replayed graph reads its clock when it runs.
@@ -39,7 +39,6 @@ namespace rg {
 namespace {
 
 constexpr uint32_t kInitLen = 148, kRespLen = 92; // HandshakeInit, HandshakeResp (rustyguard-types)
-constexpr uint32_t kItems = kGroupTile / 256;     // grouped items per lane, consecutive
 
 static_assert(sizeof(rg_rate_seed) == 16 && sizeof(rg_src_addr) == 24 && sizeof(rg_pkt_desc) == 16, "layouts");
 
@@ -55,7 +54,6 @@ struct Tables {
 struct AddOp {
     __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; }
 };
-using Pair = SegPair<uint32_t, AddOp>;
 
 // Workspace of the count call (WorkspaceCursor, rg_internal.h).  total == 0: a size is out of range.  Every term is
 // non-decreasing in n, width and depth.
@@ -89,7 +87,10 @@ __device__ __forceinline__ uint32_t sat_add(uint32_t a, uint32_t b) {
 }
 
 // ---------------------------------------------------------------- the count
+// The call's arguments; the scan kernels take them as the pass of rg_grouped.h's segscan.
 struct CountArgs {
+    using Pair = SegPair<uint32_t, AddOp>;
+    using Item = SegItem; // key = the item's bucket
     Tables t;
     const rg_pkt_desc *desc; // [n]
     const uint64_t *addrs;   // [n][3]: rg_src_addr as three words
@@ -103,6 +104,17 @@ struct CountArgs {
     uint32_t *est;         // [n * depth] workspace
     uint32_t n;
     GroupScan<uint32_t> g; // over the items: g.rows = rows, g.nrows = width * depth, g.n = n * depth
+
+    __device__ __forceinline__ void load(Item &) const {}
+    __device__ __forceinline__ uint32_t value(const Item &it) const { return it.row ? 1u : 0u; }
+    __device__ __forceinline__ void seen(const Item &) const {}
+    // upto = the bucket's counted items up to and with this one (the bucket is read only here; rate_finish
+    // writes it)
+    __device__ __forceinline__ void judge(const Item &it, uint32_t, uint32_t upto) const {
+        if (it.row) est[it.i] = sat_add(t.buckets[it.key], upto);
+    }
+    // the bucket's last item of the batch hands the count to rate_finish
+    __device__ __forceinline__ void tail(uint64_t pos, const Item &, uint32_t upto) const { tot[pos] = upto; }
 };
 
 // The filter goes on to read this message's MACs: its frame rules in its order (rg_noise.h frame_verdict), then the
@@ -128,71 +140,6 @@ __global__ __launch_bounds__(256) void rate_key_kernel(CountArgs a) {
             w = r * a.t.width + rate_column(key, s.x, s.y, a.t.width); // < width * depth <= 2^32 - 1
         }
         out[r] = w;
-    }
-}
-
-// one grouped item as the scan sees it
-struct Item {
-    uint32_t i, key; // the item, its bucket (0 for an item that rides along)
-    bool head, elig;
-};
-__device__ __forceinline__ Item load_item(const CountArgs &a, uint64_t pos, uint32_t prev_key) {
-    Item it{};
-    it.i = a.g.index_at(pos);
-    const uint32_t w = a.g.rows[it.i];
-    it.elig = a.g.has_row(w);
-    it.key = it.elig ? w : 0u;
-    it.head = pos == 0 || it.key != prev_key;
-    return it;
-}
-__device__ __forceinline__ Pair pair_of(const Item &it) { return Pair{it.head ? 1u : 0u, it.elig ? 1u : 0u}; }
-
-__global__ __launch_bounds__(256) void rate_reduce_kernel(CountArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Pair run{0u, 0u};
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item it = load_item(a, pos, prev);
-        prev = it.key;
-        run = join(run, pair_of(it));
-    }
-    Pair total;
-    (void)block_prefix(run, total);
-    if (threadIdx.x == 0) {
-        a.g.agg_flag[blockIdx.x] = total.f;
-        a.g.agg_val[blockIdx.x] = total.v;
-    }
-}
-
-__global__ __launch_bounds__(256) void rate_verdict_kernel(CountArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Item items[kItems];
-    Pair run{0u, 0u};
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos < a.g.n) {
-            items[k] = load_item(a, pos, prev);
-            prev = items[k].key;
-            run = join(run, pair_of(items[k]));
-        } else items[k] = Item{};
-    }
-    Pair total;
-    const Pair mine = block_prefix(run, total);
-    Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, mine);
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item &it = items[k];
-        ex = join(ex, pair_of(it)); // ex.v: the bucket's counted items up to and with this one
-        // (the bucket is read only here; rate_finish writes it)
-        if (it.elig) a.est[it.i] = sat_add(a.t.buckets[it.key], ex.v);
-        // the bucket's last item of the batch hands the count to rate_finish
-        if (a.g.is_tail(pos, it.key)) a.tot[pos] = ex.v;
     }
 }
 
@@ -312,10 +259,7 @@ extern "C" int rg_rate_count_batch_dev(rg_ctx *ctx, const rg_rate_tables *tables
     a.n = (uint32_t)n;
     hipLaunchKernelGGL(rg::rate_key_kernel, lanes(n), kWg, 0, st, a);
     a.g = rg::group_rows<uint32_t>(a.rows, a.t.width * a.t.depth, items, ws, L.g, st);
-    const dim3 tiles(L.g.nblk);
-    hipLaunchKernelGGL(rg::rate_reduce_kernel, tiles, kWg, 0, st, a);
-    hipLaunchKernelGGL(rg::carry_kernel<rg::Pair>, dim3(1), kWg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
-    hipLaunchKernelGGL(rg::rate_verdict_kernel, tiles, kWg, 0, st, a);
+    rg::segscan(a, st);
     hipLaunchKernelGGL(rg::rate_finish_kernel, lanes(items), kWg, 0, st, a);
     RG_HIP(hipGetLastError(), what);
     return RG_OK;

@@ -20,19 +20,16 @@
 //            sort over the window index, 8 bits per pass, as many passes as the window count needs (none
 //            for one window: the array is its own grouping)
 //   replay_clear    the (window, counter) table starts empty
-//   replay_reduce   per workgroup of 2048 grouped packets the aggregate of the segmented prefix maximum;
-//            every OK packet enters the (window, counter) table, the smallest packet index winning
-//   carry           one workgroup scans the aggregates
-//   replay_verdict  every packet's M_p, the three tests, status and undo; the running maximum at each
-//            window's last packet
+//   seg_reduce / carry / seg_verdict   rg_grouped.h's segscan with ReplayArgs as its pass.  The reduce walk:
+//            per workgroup of 2048 grouped packets the aggregate of the segmented prefix maximum; every OK
+//            packet enters the (window, counter) table, the smallest packet index winning (seen).  The
+//            verdict walk: every packet's M_p, the three tests, status and undo (judge); the running maximum
+//            at each window's last packet (tail)
 //   replay_advance  one lane per window with traffic: the slots the window moved past are cleared, last'
 //   replay_mark     the accepted packets' bits (64-bit atomic OR)
 // A packet without a window (RG_KEY_SKIP, out of range) or without a verdict to judge (any status but OK /
 // DECRYPT_ERR, RG_PKT_PENDING included) rides along in window 0's group as a neutral element and comes
 // back untouched.
-// Shared with the send-counter reservation (rg_send.hip), in rg_grouped.h: the radix passes, the grouped view
-// of the batch, the segmented pair and its workgroup scan, the carry kernel and the workspace arrays of
-// these.  The walk over a tile (8 consecutive packets a lane, their runs scanned through LDS) is this file's.
 //
 // The entry points' host side is here too (rg_cookie.hip's precedent), on rg_host.h like the host units,
 // none of which names a launcher of this file.  All scratch is the caller's workspace; nothing is
@@ -80,28 +77,8 @@ ReplayLayout replay_layout(uint64_t n, uint32_t nwin) {
     return L;
 }
 
-constexpr uint32_t kItems = kGroupTile / 256; // grouped packets per lane, consecutive
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;      // (window, counter) table: free slot (n <= 2^32 - 1)
+constexpr uint32_t kEmpty = 0xFFFFFFFFu; // (window, counter) table: free slot (n <= 2^32 - 1)
 
-// ------------------------------------------- segmented prefix maximum
-// v = the largest OK counter since the window's first packet (0 when none: every window's last is >= 0)
-struct MaxOp {
-    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
-};
-using Pair = SegPair<uint64_t, MaxOp>;
-
-struct ReplayArgs {
-    rg_antireplay *windows;
-    const uint64_t *counters; // [n]
-    uint8_t *status;          // [n]
-    uint8_t *undo;            // [n] or nullptr
-    uint32_t *hash;
-    uint64_t hash_mask;
-    uint64_t *lf;
-    GroupScan<uint64_t> g; // g.rows = the packets' window rows
-};
-
-// ------------------------------------------- (window, counter) -> earliest OK packet
 __device__ __forceinline__ uint64_t hash_slot(uint32_t w, uint64_t c, uint64_t mask) {
     uint64_t x = c ^ ((uint64_t)w * 0x9E3779B97F4A7C15ull);
     x ^= x >> 32;
@@ -112,124 +89,88 @@ __device__ __forceinline__ uint64_t hash_slot(uint32_t w, uint64_t c, uint64_t m
     return x & mask;
 }
 
-// A slot holds the index of a packet with the slot's key; packets of one key lower it to their smallest
-// index.  Once taken, a slot's key never changes, so a probe compares against whichever index it reads.
-// The table has at least two slots per packet: a probe ends.
-__device__ __forceinline__ void hash_insert(const ReplayArgs &a, uint32_t i, uint32_t w, uint64_t c) {
-    for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
-        const uint32_t e = atomicCAS(&a.hash[s], kEmpty, i);
-        if (e == kEmpty) return;
-        if (a.g.rows[e] == w && a.counters[e] == c) {
-            atomicMin(&a.hash[s], i);
-            return;
-        }
-    }
-}
-__device__ __forceinline__ uint32_t hash_find(const ReplayArgs &a, uint32_t w, uint64_t c) {
-    for (uint64_t s = hash_slot(w, c, a.hash_mask);; s = (s + 1) & a.hash_mask) {
-        const uint32_t e = a.hash[s];
-        if (e == kEmpty) return kEmpty;
-        if (a.g.rows[e] == w && a.counters[e] == c) return e;
-    }
-}
-
 __global__ __launch_bounds__(256) void replay_clear_kernel(uint4 *hash4, uint64_t quads) {
     for (uint64_t q = (uint64_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (uint64_t)gridDim.x * 256)
         hash4[q] = make_uint4(kEmpty, kEmpty, kEmpty, kEmpty);
 }
 
-// one grouped packet as the scan sees it
-struct Item {
-    uint32_t i, w, key;
-    uint32_t st; // status, or 0xFF beyond the batch
-    uint64_t ctr;
-    bool head;
+// segmented prefix maximum: v = the largest OK counter since the window's first packet (0 when none: every
+// window's last is >= 0)
+struct MaxOp {
+    __device__ __forceinline__ uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
 };
-__device__ __forceinline__ Item load_item(const ReplayArgs &a, uint64_t pos, uint32_t prev_key) {
-    Item it{};
-    it.i = a.g.index_at(pos);
-    it.w = a.g.rows[it.i];
-    const bool win = a.g.has_row(it.w);
-    it.key = win ? it.w : 0u;
-    it.st = win ? a.status[it.i] : 0xFFu;
-    it.ctr = win && it.st <= RG_PKT_DECRYPT_ERR ? a.counters[it.i] : 0ull;
-    it.head = pos == 0 || it.key != prev_key;
-    return it;
-}
-__device__ __forceinline__ Pair pair_of(const Item &it) {
-    return Pair{it.head ? 1u : 0u, it.st == RG_PKT_OK ? it.ctr : 0ull};
-}
 
-__global__ __launch_bounds__(256) void replay_reduce_kernel(ReplayArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Pair run{0u, 0ull};
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item it = load_item(a, pos, prev);
-        prev = it.key;
-        if (it.st == RG_PKT_OK) hash_insert(a, it.i, it.w, it.ctr);
-        run = join(run, pair_of(it));
-    }
-    Pair total;
-    (void)block_prefix(run, total);
-    if (threadIdx.x == 0) {
-        a.g.agg_flag[blockIdx.x] = total.f;
-        a.g.agg_val[blockIdx.x] = total.v;
-    }
-}
+// The commit's arguments; the scan kernels take them as the pass of rg_grouped.h's segscan.
+struct ReplayArgs {
+    using Pair = SegPair<uint64_t, MaxOp>;
+    struct Item : SegItem {
+        uint32_t st; // status, or 0xFF without a window
+        uint64_t ctr;
+    };
+    rg_antireplay *windows;
+    const uint64_t *counters; // [n]
+    uint8_t *status;          // [n]
+    uint8_t *undo;            // [n] or nullptr
+    uint32_t *hash;
+    uint64_t hash_mask;
+    uint64_t *lf;
+    GroupScan<uint64_t> g; // g.rows = the packets' window rows
 
-__global__ __launch_bounds__(256) void replay_verdict_kernel(ReplayArgs a) {
-    const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + threadIdx.x * kItems;
-    uint32_t prev = a.g.key_before(base);
-    Item items[kItems];
-    Pair run{0u, 0ull};
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos < a.g.n) {
-            items[k] = load_item(a, pos, prev);
-            prev = items[k].key;
-            run = join(run, pair_of(items[k]));
-        } else {
-            items[k] = Item{};
-            items[k].st = 0xFFu;
+    // (window, counter) -> earliest OK packet.  A slot holds the index of a packet with the slot's key; packets
+    // of one key lower it to their smallest index.  Once taken, a slot's key never changes, so a probe compares
+    // against whichever index it reads.  The table has at least two slots per packet: a probe ends.
+    __device__ __forceinline__ void hash_insert(uint32_t i, uint32_t w, uint64_t c) const {
+        for (uint64_t s = hash_slot(w, c, hash_mask);; s = (s + 1) & hash_mask) {
+            const uint32_t e = atomicCAS(&hash[s], kEmpty, i);
+            if (e == kEmpty) return;
+            if (g.rows[e] == w && counters[e] == c) {
+                atomicMin(&hash[s], i);
+                return;
+            }
         }
     }
-    Pair total;
-    const Pair mine = block_prefix(run, total);
-    Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, mine);
-#pragma unroll
-    for (uint32_t k = 0; k < kItems; ++k) {
-        const uint64_t pos = base + k;
-        if (pos >= a.g.n) break;
-        const Item &it = items[k];
-        const uint64_t before = it.head ? 0ull : ex.v; // largest OK counter of the window ahead of this packet
-        ex = join(ex, pair_of(it));
-        uint8_t undo = 0;
+    __device__ __forceinline__ uint32_t hash_find(uint32_t w, uint64_t c) const {
+        for (uint64_t s = hash_slot(w, c, hash_mask);; s = (s + 1) & hash_mask) {
+            const uint32_t e = hash[s];
+            if (e == kEmpty) return kEmpty;
+            if (g.rows[e] == w && counters[e] == c) return e;
+        }
+    }
+
+    __device__ __forceinline__ void load(Item &it) const {
+        it.st = it.row ? status[it.i] : 0xFFu;
+        it.ctr = it.row && it.st <= RG_PKT_DECRYPT_ERR ? counters[it.i] : 0ull;
+    }
+    __device__ __forceinline__ uint64_t value(const Item &it) const { return it.st == RG_PKT_OK ? it.ctr : 0ull; }
+    // every OK packet enters the table, the smallest packet index winning
+    __device__ __forceinline__ void seen(const Item &it) const {
+        if (it.st == RG_PKT_OK) hash_insert(it.i, it.key, it.ctr);
+    }
+    // before = the largest OK counter of the window ahead of this packet
+    __device__ __forceinline__ void judge(const Item &it, uint64_t before, uint64_t) const {
+        uint8_t u = 0;
         if (it.st <= RG_PKT_DECRYPT_ERR) { // has a window and a verdict to judge
-            const rg_antireplay &win = a.windows[it.w];
+            const rg_antireplay &win = windows[it.key];
             const uint64_t L0 = win.last, M = before > L0 ? before : L0, c = it.ctr;
             bool rej = false;
             if (c <= M) {
                 if (M - c >= RG_REPLAY_WINDOW) rej = true;
                 else if ((c >> 6) <= (L0 >> 6) && ((win.bitmap[(c >> 6) & 31] >> (c & 63)) & 1ull)) rej = true;
                 else {
-                    const uint32_t first = hash_find(a, it.w, c);
+                    const uint32_t first = hash_find(it.key, c);
                     rej = first != kEmpty && first < it.i;
                 }
             }
             if (rej) {
-                undo = it.st == RG_PKT_OK;
-                a.status[it.i] = RG_PKT_REJECTED; // also for a bad tag: would_accept comes first
+                u = it.st == RG_PKT_OK;
+                status[it.i] = RG_PKT_REJECTED; // also for a bad tag: would_accept comes first
             }
         }
-        if (a.undo) a.undo[it.i] = undo;
-        // the window's last packet of the batch hands the running maximum to replay_advance
-        if (a.g.is_tail(pos, it.key)) a.lf[pos] = ex.v;
+        if (undo) undo[it.i] = u;
     }
-}
+    // the window's last packet of the batch hands the running maximum to replay_advance
+    __device__ __forceinline__ void tail(uint64_t pos, const Item &, uint64_t upto) const { lf[pos] = upto; }
+};
 
 // One lane per window with traffic (the lane of its last grouped packet): the slots of the blocks the
 // window moved past start from zero, then last.  Both branches of mark_seen: a jump of more than 32
@@ -285,13 +226,10 @@ hipError_t launch_commit(rg_antireplay *windows, uint32_t nwin, const uint32_t *
     a.hash_mask = L.hash_cap - 1;
     a.lf = reinterpret_cast<uint64_t *>(ws + L.lf);
     a.g = group_rows<uint64_t>(win_idx, nwin, n, ws, L.g, st);
-    const dim3 tiles(L.g.nblk);
     const uint64_t quads = L.hash_cap / 4;
     hipLaunchKernelGGL(replay_clear_kernel, dim3((uint32_t)((quads + 255) / 256 < 2048 ? (quads + 255) / 256 : 2048)), wg, 0, st,
                        reinterpret_cast<uint4 *>(a.hash), quads);
-    hipLaunchKernelGGL(replay_reduce_kernel, tiles, wg, 0, st, a);
-    hipLaunchKernelGGL(carry_kernel<Pair>, dim3(1), wg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
-    hipLaunchKernelGGL(replay_verdict_kernel, tiles, wg, 0, st, a);
+    segscan(a, st);
     hipLaunchKernelGGL(replay_advance_kernel, per_packet, wg, 0, st, a);
     hipLaunchKernelGGL(replay_mark_kernel, per_packet, wg, 0, st, a);
     return hipGetLastError();

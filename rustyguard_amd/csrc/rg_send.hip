@@ -39,7 +39,6 @@ namespace rg {
 namespace {
 
 constexpr uint64_t kRejectAfterTimeNs = RG_REJECT_AFTER_TIME_NS; // lib.rs:204-209
-constexpr uint32_t kRounds = kGroupTile / 256;                   // rounds of 64 packets per wave
 
 // Workspace of the device send calls (WorkspaceCursor, rg_internal.h).  total == 0: the batch is too large.
 // Every term is non-decreasing in n and in nkeys.
@@ -97,7 +96,7 @@ struct Item {
 
 // The workgroup's tile: wave v owns the contiguous quarter v and walks it 64 positions a round.  Fills
 // items[] and returns the exclusive prefix of this wave inside the tile; `total` is the tile's aggregate.
-__device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kRounds], Pair &total) {
+__device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kTileItems], Pair &total) {
     __shared__ uint32_t s_f[4], s_v[4];
     const uint32_t t = threadIdx.x, v = t >> 6, lane = t & 63;
     const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
@@ -108,7 +107,7 @@ __device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kRoun
     uint32_t last_key = a.g.key_before(base);
     Pair run{0u, 0u};
 #pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
+    for (uint32_t r = 0; r < kTileItems; ++r) {
         const uint64_t pos = base + r * 64 + lane;
         Item it{0xFFFFFFFFu, RG_KEY_SKIP, 0u, 0u, 0u, false};
         bool head = false;
@@ -156,24 +155,21 @@ __device__ __forceinline__ Pair tile_scan(const SendArgs &a, Item (&items)[kRoun
 }
 
 __global__ __launch_bounds__(256) void send_reduce_kernel(SendArgs a) {
-    Item items[kRounds];
+    Item items[kTileItems];
     Pair total;
     (void)tile_scan(a, items, total);
-    if (threadIdx.x == 0) {
-        a.g.agg_flag[blockIdx.x] = total.f;
-        a.g.agg_val[blockIdx.x] = total.v;
-    }
+    store_tile(a.g.agg, total);
 }
 
 __global__ __launch_bounds__(256) void send_verdict_kernel(SendArgs a) {
-    Item items[kRounds];
+    Item items[kTileItems];
     Pair total;
     const Pair wave_ex = tile_scan(a, items, total);
-    const Pair ex = join(Pair{a.g.agg_flag[blockIdx.x], a.g.agg_val[blockIdx.x]}, wave_ex);
+    const Pair ex = join(tile_start<Pair>(a.g.agg), wave_ex);
     const uint32_t v = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint64_t base = (uint64_t)blockIdx.x * kGroupTile + v * (kGroupTile / 4);
 #pragma unroll
-    for (uint32_t r = 0; r < kRounds; ++r) {
+    for (uint32_t r = 0; r < kTileItems; ++r) {
         const Item &it = items[r];
         const uint64_t pos = base + r * 64 + lane;
         if (pos >= a.g.n) continue;
@@ -260,7 +256,7 @@ hipError_t launch_reserve(rg_send_state *state, uint32_t nkeys, const uint32_t *
     }
     a.g = group_rows<uint32_t>(slots, nkeys, n, ws, L.g, st);
     hipLaunchKernelGGL(send_reduce_kernel, tiles, wg, 0, st, a);
-    hipLaunchKernelGGL(carry_kernel<Pair>, dim3(1), wg, 0, st, a.g.agg_flag, a.g.agg_val, a.g.nblk);
+    hipLaunchKernelGGL(carry_kernel<Pair>, dim3(1), wg, 0, st, a.g.agg);
     hipLaunchKernelGGL(send_verdict_kernel, tiles, wg, 0, st, a);
     hipLaunchKernelGGL(send_update_kernel, per_packet, wg, 0, st, a);
     return hipGetLastError();
